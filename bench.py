@@ -33,19 +33,31 @@ region.  The frames come from a pool of 4 steps per rank rendered up front
 (a fresh batch every step, > the 256 MB MALL).
 
 Stereo (--config euroc_stereo / kitti_stereo, and the `stereo_euroc_sharded`
-leg of the default line at every N): the unit is the L/R pair one stereo
+leg of the --full line at every N): the unit is the L/R pair one stereo
 Frame is built from (src/Frame.cpp:84-98): each rank extracts the L and R
 images of its contiguous chunk of pairs in one batch and runs
 Frame::ComputeStereoMatches on them; the pair never straddles ranks, there is
 no cross-pair dependency, and every step's keypoints / descriptors / uRight /
 depth are gathered to rank 0.
 
-Also reported:
+A plain run (`bench.py --gpus N --steps K --warmup W`) is the headline alone:
+set-up, the sustained leg that brings the GPU to the clock it holds under this
+load (400 steps of the same stream, the headline's warm-up and timed steps
+queued straight behind it), W warm-up steps, exactly K timed steps, and the
+result line (value, ms_per_step, and what the timed steps' own events give:
+stage times and the pyramid roofline below).  --dump-outputs DIR then writes
+what the last timed step delivered as DIR/<name>.npy (float32: counts, match
+counts, and keypoints / descriptors / m12 rows of a fixed seeded sample of at
+most 64 frames; same arguments, same inputs, same files).  Everything else
+listed below runs with --full only.
+
+Reported (all but the roofline with --full):
   * roofline: the pyramid pass (the HBM-bound stage named by BASELINE.json),
     algorithmic bytes = sum_{l>=1} |P_{l-1}| + |P_l| per frame, divided by the
     pyramid launches' summed duration from HIP events recorded on the launch
     stream during the timed region; traffic = PMC-measured HBM bytes from
     profiles/ when a matching summary exists;
+  * parity_vs_oracle: the last timed step's outputs against the CPU oracle;
   * cpu_baseline: the oracle (a scalar C++ restatement, oracle/liborbref.so --
     NOT the reference's SIMD OpenCV code) on the host cores, rank 0 at N=1
     only, on a bounded sample;
@@ -136,7 +148,7 @@ def parse(argv=None):
                          "gpu0 = counts then used rows sent to rank 0's HBM")
     ap.add_argument("--feed", default="hbm", choices=["hbm", "host"],
                     help="headline input: frames resident in HBM (default) or copied from pinned host memory "
-                         "every step (the host_fed leg of the default line)")
+                         "every step (the host_fed leg of the --full line)")
     ap.add_argument("--parts", type=int, default=1,
                     help="headline step as this many sub-batches on their own streams, each started once the "
                          "previous one has passed --part-stage (1: one extraction of the whole batch)")
@@ -144,15 +156,27 @@ def parse(argv=None):
     ap.add_argument("--match-priority", type=int, default=0, choices=[0, -1],
                     help="matcher stream priority (0: default, below the extraction streams; -1: high)")
     ap.add_argument("--sustained-steps", type=int, default=None,
-                    help="length of the mono line's sustained leg (default: BENCH_SUSTAINED_STEPS or 400 with the "
-                         "extra legs on a GPU, none otherwise; > 0 forces it, e.g. in the CPU launcher tests)")
+                    help="length of the mono line's sustained leg (default: BENCH_SUSTAINED_STEPS or 400 on a "
+                         "GPU, with --full at least --steps; none with --no-extras or on the CPU; > 0 forces it, "
+                         "e.g. in the CPU launcher tests)")
     ap.add_argument("--other-delivery", type=int, default=1, choices=[0, 1],
                     help="N > 1: also run the stream with the other --deliver mode (a second leg in the line)")
     ap.add_argument("--traffic-json", default=str(ROOT / "profiles" / "pmc_traffic.json"))
     ap.add_argument("--cpu-dry-run", default=None, metavar="ENGINE.py",
                     help="tests only: gloo on the CPU with ENGINE.py standing in for orbgpu")
     ap.add_argument("--dump", default=None, metavar="DIR", help="rank 0 writes every step's gathered outputs")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: parity against the oracle, CPU baselines, the other "
+                         "delivery mode, host-fed / stereo / loop-burst / other-geometry legs, drop-in latencies "
+                         "(--no-extras and --no-cpu-baseline take their parts out again)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes the last timed step's outputs as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of the frames when the batch is large)")
+    args = ap.parse_args(argv)
+    # a plain run is the headline alone; --full adds the rest, as far as the --no-* options leave it in
+    args.extras = args.full and not args.no_extras
+    args.cpu_base = args.full and not args.no_cpu_baseline
+    return args
 
 
 SUSTAINED_STEPS = int(os.environ.get("BENCH_SUSTAINED_STEPS", "400"))  # the sustained leg of the mono line
@@ -316,6 +340,43 @@ class _Dumper:
         for k in keys:
             out[k] = np.stack([self.rows[u][k] for u in units])
         np.savez(Path(self.path) / f"{self.name}.npz", **out)
+
+
+DUMP_UNITS = 64  # --dump-outputs: units (frames, pairs, KF pairs) written when the batch holds more
+
+
+def dump_sample(n, limit=DUMP_UNITS):
+    """the units --dump-outputs writes: all n, or a fixed seeded sample of them in ascending order"""
+    if n <= limit:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0xD0).choice(n, limit, replace=False))
+
+
+def trim_rows(a, counts, fill=0):
+    """(n, cap, ...) rows as float32, row i of unit u >= counts[u] set to `fill` (rows past a
+    unit's count hold whatever an earlier step left there; a caller never reads them)"""
+    a = np.asarray(a).astype(np.float32)
+    past = np.arange(a.shape[1])[None, :] >= np.asarray(counts).reshape(-1, 1)
+    a[past] = fill
+    return a
+
+
+def keypoint_values(raw):
+    """(..., 7) keypoint records read as float32 (orbgpu_keypoint) -> their values as float32:
+    x, y, size, angle, response, and octave / class_id, stored as int32, converted"""
+    raw = np.ascontiguousarray(raw, np.float32)
+    out = raw.copy()
+    out[..., 5:] = raw[..., 5:].view(np.int32)
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one float32 / float64 .npy per output"""
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32)))
 
 
 # ---------------------------------------------------------------------------
@@ -751,6 +812,20 @@ class StreamBench:
     def close(self):
         self.delivery.close()
 
+    def outputs(self):
+        """--dump-outputs: what the last timed step delivers, from its output set on this
+        rank: every frame's keypoint count, the count of the frame it was matched against and
+        its SearchForInitialization match count; for the sampled frames (`frames`) the
+        keypoints (7 fields), descriptors and m12 rows, rows past the counts cleared."""
+        self.D.synchronize()
+        S = self.sets[(self.step_no - 1) % NSETS]
+        idx = dump_sample(self.B)
+        sel = torch.as_tensor(idx, device=self.dev)
+        cnt, c1 = S.counts.cpu().numpy(), S.c1.cpu().numpy()
+        return {"frames": idx, "counts": cnt, "counts_f1": c1, "nmatch": S.nmatch.cpu().numpy(),
+                "keypoints": trim_rows(keypoint_values(S.kps[sel].cpu().numpy()), cnt[idx]),
+                "descriptors": trim_rows(S.desc[sel].cpu().numpy(), cnt[idx]),
+                "matches12": trim_rows(S.m12[sel].cpu().numpy(), c1[idx], fill=-1)}
 
     def parity_timed(self):
         """The timed path's own outputs against the oracle (untimed, after run()):
@@ -925,6 +1000,23 @@ class StereoBench:
                     "from": f"output set of the last timed step ({P} pairs, the timed extractor and stereo launch)"}
         except Exception as e:  # report, never hide
             return {"ok": False, "error": str(e)}
+
+    def outputs(self):
+        """--dump-outputs: the last timed step's output set on this rank: every frame's
+        keypoint count (L, R per pair); for the sampled pairs (`pairs`) both frames'
+        keypoints and descriptors and the left frame's uRight / depth, rows past the counts
+        cleared."""
+        self.D.synchronize()
+        kps, desc, counts, ur, dp = self.sets[(self.step_no - 1) % 2]
+        idx = dump_sample(self.P, DUMP_UNITS // 2)  # two frames per pair
+        fr = np.stack([2 * idx, 2 * idx + 1], 1).reshape(-1)
+        sel, fsel = torch.as_tensor(idx, device=self.dev), torch.as_tensor(fr, device=self.dev)
+        cnt = counts.cpu().numpy()
+        return {"pairs": idx, "counts": cnt,
+                "keypoints": trim_rows(keypoint_values(kps[fsel].cpu().numpy()), cnt[fr]),
+                "descriptors": trim_rows(desc[fsel].cpu().numpy(), cnt[fr]),
+                "uright": trim_rows(ur[sel].cpu().numpy(), cnt[2 * idx], fill=-1),
+                "depth": trim_rows(dp[sel].cpu().numpy(), cnt[2 * idx], fill=-1)}
 
     def summary(self, r, steps):
         return {"pairs_per_s": round(r["pairs_per_s"], 1), "ms_per_step": round(r["elapsed"] / steps * 1e3, 3),
@@ -1313,7 +1405,7 @@ class LoopLeg:
                                                       outlier_frac=ofr, seed=seed, fix_scale=fix)
         return self.scenes[mix]
 
-    def run(self, mix, steps, warmup):
+    def run(self, mix, steps, warmup, parity=True, dump_outputs=None):
         import loop
         nq, nc, dev = self.nq, self.nc, self.dev
         scene = self.scene(mix)
@@ -1352,7 +1444,20 @@ class LoopLeg:
         res = lb.query_results()
         states = lb.candidate_states()
         # the timed burst's own outputs against the oracle (untimed): rank 0's first and last query
-        self.last_parity = self.parity_timed(lb, mix, my_q, res, states) if self.rank == 0 else None
+        self.last_parity = self.parity_timed(lb, mix, my_q, res, states) if (self.rank == 0 and parity) else None
+        if dump_outputs and self.rank == 0:
+            # this rank's burst as ComputeSim3 returns it: per KF pair the SearchByBoW match count and
+            # (sampled pairs) vpMatches12; per query the matched candidate, its round, inliers and Sim3
+            idx = dump_sample(len(my_q) * nc)
+            nmh = lb.nmatches.cpu().numpy()
+            write_outputs(dump_outputs, {
+                "kf_pairs": idx, "nmatches": nmh,
+                "matches12": lb.match[torch.as_tensor(idx, device=dev)].cpu().numpy(),
+                "matched": [r.matched for r in res], "round": [r.round for r in res],
+                "n_inliers": [r.n_inliers for r in res], "hypotheses": [r.hypotheses for r in res],
+                "R12": np.array([list(r.R12) for r in res], np.float32),
+                "t12": np.array([list(r.t12) for r in res], np.float32),
+                "s12": np.array([r.s12 for r in res], np.float32)})
         n_kp = 1000
         npairs = len(my_q) * nc
         sbb_bytes = 2 * n_kp * (32 + 4 + 1 + 4 + 4) + n_kp * 4
@@ -1459,13 +1564,19 @@ class LoopLeg:
                           f"threads' draws interleave (timing only)"}
 
 
-def run_loop_leg(args, rank, world, dev, mixes, info=None):
+def run_loop_leg(args, rank, world, dev, mixes, info=None, headline=False):
+    """the loop-burst mixes as a leg of the mono line (5..20 steps each, with parity), or with
+    headline=True as --config loopburst's own figure: the `bench` mix over exactly --steps
+    timed steps after --warmup, parity and the other mixes only with --full"""
     leg = LoopLeg(rank, world, dev)
     out = {"vocabulary": "k=10 L=6 (1,111,111 nodes), DBoW2 text format, loaded by orbgpu_vocabulary_load_text",
            "setup_s": round(leg.t_voc, 2), "vocabulary_text_load_s": round(leg.t_load, 2)}
     steps, warm = max(5, min(args.steps, 20)), 2
     for mix in mixes:
-        out[mix] = leg.run(mix, steps, warm)
+        if headline and mix == "bench":
+            out[mix] = leg.run(mix, args.steps, args.warmup, parity=args.full, dump_outputs=args.dump_outputs)
+        else:
+            out[mix] = leg.run(mix, steps, warm)
     if info is not None:
         for mix in mixes:
             out[mix]["cpu_baseline"] = leg.cpu_baseline(mix, args.cpu_seconds / 2, info)
@@ -1492,8 +1603,9 @@ def common_line(args, world):
 
 
 def main_loopburst(args, rank, world, dev):
-    info = cpu_info() if (world == 1 and not args.no_cpu_baseline and rank == 0) else None
-    legs, _ = run_loop_leg(args, rank, world, dev, ["bench", "several_rounds", "false_loops"], info)
+    info = cpu_info() if (world == 1 and args.cpu_base and rank == 0) else None
+    mixes = ["bench", "several_rounds", "false_loops"] if args.full else ["bench"]
+    legs, _ = run_loop_leg(args, rank, world, dev, mixes, info, headline=True)
     if rank != 0:
         return None
     b = legs["bench"]
@@ -1520,7 +1632,9 @@ def main_stereo(args, og, D, rank, world, stream):
     r = sb.run(args.warmup, args.steps)
     if rank != 0:
         return None
-    parity = sb.parity_timed()
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, sb.outputs())
+    parity = sb.parity_timed() if args.full else None
     W, H, NF, desc = CONFIGS[args.config]
     line = {"metric": f"pairs/sec stereo Frame (extract L+R + ComputeStereoMatches, {W}x{H}, {NF} feat)",
             "value": round(r["pairs_per_s"], 1), "unit": "pairs/s", **common_line(args, world),
@@ -1530,7 +1644,7 @@ def main_stereo(args, og, D, rank, world, stream):
             "keypoints_per_frame": round(r["keypoints_per_frame"], 1),
             "left_keypoints_with_depth": round(r["left_keypoints_with_depth"], 3),
             "parity_vs_oracle": parity}
-    if D.cuda and world == 1 and not args.no_cpu_baseline:
+    if D.cuda and world == 1 and args.cpu_base:
         line["cpu_baseline"] = cpu_baseline_stereo(args.config, args.cpu_seconds, cpu_info())
     return line
 
@@ -1543,8 +1657,12 @@ def main_mono(args, og, D, rank, world, stream):
     sb = StreamBench(og, D, W, H, NF, B, rank, world, stream, dump=args.dump, deliver=args.deliver, feed=args.feed,
                      parts=args.parts, part_stage=args.part_stage)
     extras = {}
-    n_sus = args.sustained_steps if args.sustained_steps is not None else (
-        max(args.steps, SUSTAINED_STEPS) if not args.no_extras and D.cuda else 0)
+    if args.sustained_steps is not None:
+        n_sus = args.sustained_steps
+    elif args.no_extras or not D.cuda:
+        n_sus = 0
+    else:  # a plain run keeps the leg, at its shortest: the headline is timed at the clock it leaves
+        n_sus = max(args.steps, SUSTAINED_STEPS) if args.full else SUSTAINED_STEPS
     if n_sus > 0:
         # sustained leg, before the headline: the same stream for SUSTAINED_STEPS steps
         # (~0.55 s at 640x480; the headline's timed region is steps x ms_per_step, ~30 ms at
@@ -1570,11 +1688,13 @@ def main_mono(args, og, D, rank, world, stream):
     else:
         r = sb.run(args.warmup, args.steps)
     # the timed configuration's own outputs against the oracle (rank 0, untimed)
-    parity = sb.parity_timed() if rank == 0 else None
+    parity = sb.parity_timed() if (rank == 0 and args.full) else None
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, sb.outputs())
     sb.close()
     del sb
     D.empty_cache()
-    if world > 1 and args.other_delivery:
+    if world > 1 and args.other_delivery and args.full:
         # the other delivery mode on the same stream (N > 1): per rank ms_per_step and the
         # owner's waits for both modes in one line
         other = "host" if args.deliver == "gpu0" else "gpu0"
@@ -1589,7 +1709,7 @@ def main_mono(args, og, D, rank, world, stream):
             "ms_per_step": round(orr["elapsed"] / args.steps * 1e3, 3), "delivery": orr["delivery"],
             "stages_ms_per_step_rank0": {k: round(v, 4) for k, v in orr["per_step"].items()},
             "note": "the same stream and steps with the other delivery mode, run after the headline"}
-    if not args.no_extras and D.cuda and args.feed == "hbm":
+    if args.extras and D.cuda and args.feed == "hbm":
         # host-fed leg: the same stream with every step's frames copied from pinned host
         # memory (double-buffered H2D on a copy stream, overlapped with extraction) and the
         # outputs delivered to host memory, as TrackMonocular consumes them
@@ -1607,7 +1727,7 @@ def main_mono(args, og, D, rank, world, stream):
             "bound": ("pcie_h2d" if h2d_ms and h2d_ms > compute_ms else "kernels"),
             "workload": desc_cfg + "; frames copied from pinned host memory every step (H2D on a copy stream, "
                                    "double-buffered), outputs delivered to pinned host memory"}
-    if not args.no_extras and D.cuda:
+    if args.extras and D.cuda:
         # config 4: EuRoC stereo sharded over all ranks (every N)
         esb = StereoBench(og, D, "euroc_stereo", 128, rank, world, stream)
         er = esb.run(2, 10)
@@ -1617,7 +1737,7 @@ def main_mono(args, og, D, rank, world, stream):
         del esb
         D.empty_cache()
         # config 5: loop-closure bursts, queries round-robin over all ranks
-        info = cpu_info() if (world == 1 and not args.no_cpu_baseline and rank == 0) else None
+        info = cpu_info() if (world == 1 and args.cpu_base and rank == 0) else None
         loop_legs, _ = run_loop_leg(args, rank, world, D.device, ["bench", "several_rounds", "false_loops"], info)
         extras["loop_burst"] = loop_legs
         D.empty_cache()
@@ -1661,8 +1781,8 @@ def main_mono(args, og, D, rank, world, stream):
     if tr and r["per_step"].get("pyramid"):
         line["roofline"]["traffic_frac"] = round(tr / (r["per_step"]["pyramid"] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
     line.update(extras)
-    if world == 1 and not args.no_extras and D.cuda:
-        line["drop_in"] = drop_in_latency(with_cpu=not args.no_cpu_baseline)
+    if world == 1 and args.extras and D.cuda:
+        line["drop_in"] = drop_in_latency(with_cpu=args.cpu_base)
         ex_op = line["drop_in"].get("ops", {}).get("ORBextractor::operator()")
         if ex_op:
             line["single_frame"] = {"median_ms": round(ex_op["median_us"] / 1e3, 4),
@@ -1690,7 +1810,7 @@ def main_mono(args, og, D, rank, world, stream):
         del ksb
         D.empty_cache()
         line["other_geometries"] = other
-    if world == 1 and not args.no_cpu_baseline and D.cuda:
+    if world == 1 and args.cpu_base and D.cuda:
         import synth
         info = cpu_info()
         frames_np = np.stack([synth.torch_stream(1, W, H, device=D.device, t0=t, bounded=True)[0].cpu().numpy()

@@ -30,13 +30,14 @@ ENGINE = ROOT / "tests" / "dryrun_orbgpu.py"
 
 
 def _run_bench(tmp_path, *args, timeout=420, world=2):
+    """--full: the parity against the oracle and the other delivery mode's leg are not part of a plain run"""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     env.pop("LOCAL_RANK", None)
     env["OMP_NUM_THREADS"] = "2"
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--cpu-dry-run", str(ENGINE), "--dump",
-           str(tmp_path), "--no-cpu-baseline", "--no-extras", *args]
+           str(tmp_path), "--full", "--no-cpu-baseline", "--no-extras", *args]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=str(ROOT))
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -203,6 +204,53 @@ def test_stereo_pairs_two_ranks_equal_single_process(tmp_path):
             assert got["uright"][pair][:len(kl)].tobytes() == ur.tobytes()
             assert got["depth"][pair][:len(kl)].tobytes() == dp.tobytes()
             assert (ur >= 0).sum() > 0.3 * len(kl)  # a real stereo scene
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing that takes a run or a
+    reference of its own; --dump-outputs writes the last timed step's output set as float32
+    arrays, rows past the counts cleared, equal to the oracle on the same frames (pair 0's
+    F1 is the previous step's last frame)."""
+    import orbref
+    import synth
+    B, steps = 2, 2
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["OMP_NUM_THREADS"] = "2"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--cpu-dry-run", str(ENGINE), "--batch", str(B),
+           "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=str(ROOT))
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-3000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    for k in ("delivery_other_mode", "host_fed", "stereo_euroc_sharded", "loop_burst", "drop_in",
+              "other_geometries", "cpu_baseline"):
+        assert k not in line, k
+    assert line["parity_vs_oracle"] is None
+    got = {f.stem: np.load(f) for f in (tmp_path / "out").glob("*.npy")}
+    assert sorted(got) == ["counts", "counts_f1", "descriptors", "frames", "keypoints", "matches12", "nmatch"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert list(got["frames"]) == list(range(B))
+    # the last of the 1 + 2 steps: frames [2B, 3B), matched against frames [2B - 1, 3B - 1)
+    imgs = np.concatenate([synth.torch_stream(B, 640, 480, device="cpu", pitch=640, bounded=True, t0=s * B).numpy()
+                           for s in (1, 2)])
+    ex = orbref.Extractor(1000)
+    ref = [ex.extract(imgs[i]) for i in range(B - 1, 2 * B)]
+    cap = got["keypoints"].shape[1]
+    for b in range(B):
+        (k1, d1), (k, d) = ref[b], ref[b + 1]
+        n = len(k)
+        nm, m12, _ = orbref.search_for_initialization(k1, d1, k, d, 640, 480)
+        assert got["counts"][b] == n and got["counts_f1"][b] == len(k1) and got["nmatch"][b] == nm
+        vals = np.stack([k[f].astype(np.float32) for f in k.dtype.names], 1)  # octave, class_id as values
+        assert got["keypoints"][b, :n].tobytes() == vals.tobytes()
+        assert np.array_equal(got["descriptors"][b, :n], d.astype(np.float32))
+        assert np.array_equal(got["matches12"][b, :len(k1)], m12.astype(np.float32))
+        assert not got["keypoints"][b, n:].any() and not got["descriptors"][b, n:].any()
+        assert (got["matches12"][b, len(k1):] == -1).all() and cap >= n
 
 
 @pytest.mark.gpu

@@ -16,10 +16,15 @@ oracle/ref_shim.cpp.  Against that binary:
   weighting (TF_IDF, TF, IDF, BINARY) and the L1 / L2 / DOT_PRODUCT scorings.
 
 The GPU test library is loaded without a device for the RNG (host code).
-When oracle/_ref is absent (a box without /root/reference that was not given
-the prebuilt .so) the tests skip.
+What that binary returned for these tests' inputs is stored in
+tests/golden/refpin.npz (tools/make_refpin_golden.py, with the inputs of the
+BowVector cases): where oracle/_ref is absent the tests compare against the
+stored vectors, and where it is present against both.
 """
 import ctypes
+import json
+import subprocess
+import sys
 from pathlib import Path
 
 import numpy as np
@@ -27,12 +32,19 @@ import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
 REFLIB = ROOT / "oracle" / "_ref" / "libdbow2ref.so"
+GOLDEN = ROOT / "tests" / "golden" / "refpin.npz"
+SEEDS = [0, 1, 2, 12345, 2 ** 31 - 1]
 
 
 @pytest.fixture(scope="module")
-def ref():
+def gold():
+    return dict(np.load(GOLDEN))
+
+
+def _load_ref():
+    """the reference binary, or None where it is not built (the stored vectors stand in)"""
     if not REFLIB.exists():
-        pytest.skip("oracle/_ref/libdbow2ref.so not built (make -C oracle -f ref.mk)")
+        return None
     L = ctypes.CDLL(str(REFLIB))
     vp, i = ctypes.c_void_p, ctypes.c_int
     L.ref_seed_rand_once.argtypes = [i]
@@ -41,6 +53,11 @@ def ref():
     L.ref_random_int.restype = i
     L.ref_bow_vectors.argtypes = [i, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp]
     return L
+
+
+@pytest.fixture(scope="module")
+def ref():
+    return _load_ref()
 
 
 def _ranges(seed=0, n=6000):
@@ -54,39 +71,75 @@ def _ranges(seed=0, n=6000):
     return out[:n]
 
 
-def test_random_int_stream_equals_reference_dutils(ref):
+def test_random_int_stream_equals_reference_dutils(ref, gold):
     """Initializer.cpp:102 SeedRandOnce(0), then RandomInt over the draws of
     the minimal-set loops; glibc seeds 0 and 1 give the same stream."""
-    import orbgpu
-    lib = orbgpu.lib()
-    lib.orbgpu_seed_rand_once.argtypes = [ctypes.c_uint]
-    lib.orbgpu_random_int.restype = ctypes.c_int
-    ref.ref_seed_rand_once(0)
-    lib.orbgpu_srand(7)  # a different state first: SeedRandOnce(0) must reset it
-    lib.orbgpu_seed_rand_once(0)
+    # "once" is per process on both sides, and any earlier test that ran the Initializer has
+    # used this process's: the first call has to be the first of a fresh process
     rs = _ranges()
+    out = subprocess.run([sys.executable, "-c", _ONCE_CHILD, str(REFLIB) if ref is not None else ""],
+                         input=json.dumps(rs), capture_output=True, text=True, timeout=120, cwd=str(ROOT))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    r = json.loads(out.stdout.splitlines()[-1])
+    wants = [(list(gold["once_first"]), list(gold["once_second"]))]
+    if ref is not None:
+        wants.append((r["want"], r["want_second"]))
+    for want, want_second in wants:
+        assert len(want) == len(rs) and r["got"] == want
+        # SeedRandOnce is once per process in the reference: a second call keeps the stream going
+        assert len(want_second) == 500 and r["got_second"] == want_second
+
+
+_ONCE_CHILD = """
+import ctypes, json, sys
+sys.path[:0] = ["orb-slam2-annotation_amd"]
+import orbgpu
+ref = None
+if sys.argv[1]:
+    ref = ctypes.CDLL(sys.argv[1])
+    i = ctypes.c_int
+    ref.ref_seed_rand_once.argtypes = [i]
+    ref.ref_random_int.argtypes = [i, i]
+    ref.ref_random_int.restype = i
+lib = orbgpu.lib()
+lib.orbgpu_seed_rand_once.argtypes = [ctypes.c_uint]
+lib.orbgpu_random_int.restype = ctypes.c_int
+rs = json.loads(sys.stdin.read())
+want = want2 = None
+if ref is not None:
+    ref.ref_seed_rand_once(0)
     want = [ref.ref_random_int(a, b) for a, b in rs]
-    got = [lib.orbgpu_random_int(a, b) for a, b in rs]
-    assert got == want
-    # SeedRandOnce is once per process in the reference: a second call keeps the stream going
     ref.ref_seed_rand_once(123)
-    lib.orbgpu_seed_rand_once(123)
-    assert [lib.orbgpu_random_int(0, 99) for _ in range(500)] == [ref.ref_random_int(0, 99) for _ in range(500)]
+    want2 = [ref.ref_random_int(0, 99) for _ in range(500)]
+lib.orbgpu_srand(7)  # a different state first: SeedRandOnce(0) must reset it
+lib.orbgpu_seed_rand_once(0)
+got = [lib.orbgpu_random_int(a, b) for a, b in rs]
+lib.orbgpu_seed_rand_once(123)
+got2 = [lib.orbgpu_random_int(0, 99) for _ in range(500)]
+print(json.dumps({"got": got, "want": want, "got_second": got2, "want_second": want2}))
+"""
 
 
-@pytest.mark.parametrize("seed", [0, 1, 2, 12345, 2 ** 31 - 1])
-def test_seeded_stream_equals_reference_dutils(ref, seed):
+@pytest.mark.parametrize("seed", SEEDS)
+def test_seeded_stream_equals_reference_dutils(ref, gold, seed):
     """DUtils::Random::SeedRand(seed) (= srand) vs orbgpu_srand(seed)"""
     import orbgpu
     lib = orbgpu.lib()
     lib.orbgpu_random_int.restype = ctypes.c_int
-    ref.ref_seed_rand(seed)
     lib.orbgpu_srand(seed & 0xFFFFFFFF)
     rs = _ranges(seed, 2000)
-    assert [lib.orbgpu_random_int(a, b) for a, b in rs] == [ref.ref_random_int(a, b) for a, b in rs]
+    got = [lib.orbgpu_random_int(a, b) for a, b in rs]
+    assert len(gold[f"seed_{seed}"]) == len(rs) and got == list(gold[f"seed_{seed}"])
+    if ref is not None:
+        ref.ref_seed_rand(seed)
+        assert got == [ref.ref_random_int(a, b) for a, b in rs]
 
 
-def _ref_vectors(ref, words, nodes, weights, weighting, scoring):
+GOLD_PARTS = ("bow_words", "bow_values", "fv_nodes", "fv_offsets", "fv_features")
+
+
+def _ref_raw(ref, words, nodes, weights, weighting, scoring):
+    """the reference's BowVector (words, values) and FeatureVector (CSR) as arrays"""
     n = len(words)
     m = max(n, 1)
     w = np.ascontiguousarray(words, np.int32)
@@ -98,8 +151,23 @@ def _ref_vectors(ref, words, nodes, weights, weighting, scoring):
     ref.ref_bow_vectors(n, w.ctypes.data, nd.ctypes.data, wt.ctypes.data, weighting, scoring, bw.ctypes.data,
                         bv.ctypes.data, ctypes.byref(bn), fn.ctypes.data, fo.ctypes.data, ff.ctypes.data,
                         ctypes.byref(fvn))
-    bow = {int(bw[i]): float(bv[i]) for i in range(bn.value)}
-    fv = {int(fn[i]): list(ff[fo[i]:fo[i + 1]]) for i in range(fvn.value)}
+    b, f = bn.value, fvn.value
+    return bw[:b].copy(), bv[:b].copy(), fn[:f].copy(), fo[:f + 1].copy(), ff[:fo[f]].copy()
+
+
+def _ref_vectors(ref, gold, key, words, nodes, weights, weighting, scoring):
+    """BowVector / FeatureVector of the reference for these per-feature (word, node,
+    weight): the stored ones (recorded for exactly these inputs), and the binary's where it
+    is built -- then the two must be the same bits"""
+    for name, a, dt in (("words", words, np.int32), ("nodes", nodes, np.int32), ("weights", weights, np.float64)):
+        assert np.ascontiguousarray(a, dt).tobytes() == gold[f"{key}_{name}"].tobytes(), (key, name)
+    raw = tuple(gold[f"{key}_{p}"] for p in GOLD_PARTS)
+    if ref is not None:
+        live = _ref_raw(ref, words, nodes, weights, weighting, scoring)
+        assert all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(raw, live)), key
+    bw, bv, fn, fo, ff = raw
+    bow = {int(bw[i]): float(bv[i]) for i in range(len(bw))}
+    fv = {int(fn[i]): list(ff[fo[i]:fo[i + 1]]) for i in range(len(fn))}
     return bow, fv
 
 
@@ -111,7 +179,7 @@ CASES = [(wgt, sc) for wgt in (0, 1, 2, 3) for sc in (0, 1, 5)]
 
 
 @pytest.mark.parametrize("weighting,scoring", CASES)
-def test_oracle_bow_vectors_equal_reference_dbow2(ref, weighting, scoring):
+def test_oracle_bow_vectors_equal_reference_dbow2(ref, gold, weighting, scoring):
     """oracle/bow_ref.py's BowVector / FeatureVector vs the reference's
     compiled BowVector / FeatureVector fed the oracle's (word, node, weight)"""
     import bow_ref
@@ -120,14 +188,14 @@ def test_oracle_bow_vectors_equal_reference_dbow2(ref, weighting, scoring):
     voc = bow_ref.Vocabulary.from_arrays(8, 4, scoring, weighting, par, leaf, desc, w)
     D = synth.bow_frame_pair(desc[leaf == 1], 700, 0.5, seed=3)[0]
     words, nodes, weights, fv, bow = voc.transform(D, 2)
-    rb, rf = _ref_vectors(ref, words, nodes, weights, weighting, scoring)
+    rb, rf = _ref_vectors(ref, gold, f"oracle_{weighting}_{scoring}", words, nodes, weights, weighting, scoring)
     assert {k: list(v) for k, v in fv.items()} == rf
     assert _bits(bow) == _bits(rb)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("weighting,scoring", CASES)
-def test_gpu_bow_vectors_equal_reference_dbow2(ref, weighting, scoring):
+def test_gpu_bow_vectors_equal_reference_dbow2(ref, gold, weighting, scoring):
     """csrc/bow.hip's BowVector / FeatureVector (orbgpu_bow_transform) vs the
     reference's compiled BowVector / FeatureVector fed the GPU's own
     (word, node, weight) per feature, bit for bit"""
@@ -138,7 +206,8 @@ def test_gpu_bow_vectors_equal_reference_dbow2(ref, weighting, scoring):
     for seed in (1, 2):
         D = synth.bow_frame_pair(desc[leaf == 1], 1000, 0.5, seed=seed)[0]
         words, nodes, weights, fv, bw = voc.transform(D, 4)
-        rb, rf = _ref_vectors(ref, words, nodes, weights, weighting, scoring)
+        rb, rf = _ref_vectors(ref, gold, f"gpu_{weighting}_{scoring}_{seed}", words, nodes, weights, weighting,
+                              scoring)
         assert {k: list(v) for k, v in fv.items()} == rf
         assert _bits(bw) == _bits(rb)
         assert len(rb) > 100
