@@ -1,12 +1,21 @@
-// host_common.h -- error reporting and device checks shared by the host
-// translation units of liborbgpu.so (orbgpu.cpp, ransac.cpp).
+// host_common.h -- what the host translation units of liborbgpu.so share:
+// error reporting and device checks (host_common.cpp), owning holders of HIP
+// handles, and the one reader of the ORBGPU_* environment knobs.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <string>
 
 #include "../../include/orbgpu.h"
+
+#define ORB_HIP(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return ::orbgpu::fail(ORBGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
 
 namespace orbgpu {
 
@@ -40,11 +49,49 @@ class DeviceScope {
     int prev_ = -1;
 };
 
-}  // namespace orbgpu
+// Move-only owner of one HIP handle, released when the owner goes.  It converts
+// to the raw handle (what the launchers take); put() is the out-parameter of
+// the creating call (hipMalloc, hipStreamCreate, ...).
+template <class H, class Arg, hipError_t (*Release)(Arg)>
+class Owned {
+  public:
+    Owned() = default;
+    Owned(Owned&& o) noexcept : h_(o.release()) {}
+    Owned& operator=(Owned&& o) noexcept { reset(o.release()); return *this; }
+    ~Owned() { reset(); }
+    H get() const { return h_; }
+    operator H() const { return h_; }
+    H* put() { reset(); return &h_; }
+    H release() { H h = h_; h_ = nullptr; return h; }
+    void reset(H h = nullptr) { if (h_) (void)Release(h_); h_ = h; }
 
-#define ORB_HIP(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return ::orbgpu::fail(ORBGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+  private:
+    H h_ = nullptr;
+};
+template <class T> using DevBuf = Owned<T*, void*, hipFree>;      // hipMalloc, hipExtMallocWithFlags
+template <class T> using PinBuf = Owned<T*, void*, hipHostFree>;  // hipHostMalloc
+using Stream = Owned<hipStream_t, hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEvent_t, hipEventDestroy>;
+
+// `count` elements of HBM (at least one, so the pointer is never null)
+template <class T>
+int dalloc(DevBuf<T>& p, size_t count) {
+    if (count == 0) count = 1;
+    ORB_HIP(hipMalloc((void**)p.put(), count * sizeof(T)));
+    return ORBGPU_OK;
+}
+
+// The ORBGPU_* environment knobs: atoi of the variable, `def` when it is unset;
+// ranges are clamped where the knob is used.  env_now_int reads the environment
+// at every call -- for the knobs a test switches within one process, and only
+// those.  ORB_ENV_ONCE_INT / _FLAG read it at their first evaluation and keep
+// that value for the process (a flag is off only when set to 0).
+inline int env_now_int(const char* name, int def) {
+    const char* s = std::getenv(name);
+    return s ? std::atoi(s) : def;
+}
+#define ORB_ENV_ONCE_INT(name, def) \
+    ([] { static const int v_ = ::orbgpu::env_now_int(name, def); return v_; }())
+#define ORB_ENV_ONCE_FLAG(name, default_on) (ORB_ENV_ONCE_INT(name, (default_on) ? 1 : 0) != 0)
+
+}  // namespace orbgpu

@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -29,13 +28,7 @@
 namespace orbgpu {
 
 // transfers of the host-form calls by copy kernels (default) or the copy engine
-inline bool host_copy_kernels() {
-    static const bool v = [] {
-        const char* s = std::getenv("ORBGPU_HOST_ZEROCOPY");
-        return !(s && std::atoi(s) == 0);
-    }();
-    return v;
-}
+inline bool host_copy_kernels() { return ORB_ENV_ONCE_FLAG("ORBGPU_HOST_ZEROCOPY", true); }
 
 struct HostCtx {
     hipStream_t stream = nullptr;

@@ -14,9 +14,9 @@
 // GetFeaturesInArea order (cell ix outer, iy inner, index) -- and a second
 // reduction for bestDist2.  The rotation histogram, ComputeThreeMaxima and
 // the cull run on the same wave.
-#include <cstdlib>
 #include <type_traits>
 
+#include "host_common.h"
 #include "orbgpu_internal.h"
 #include "orbgpu_kernels.h"
 #include "../../include/orbgpu.h"
@@ -533,18 +533,13 @@ __global__ __launch_bounds__(256) void hamming_pairs_kernel(const uint8_t* __res
 // drop-in's one) take 1024 threads, the shortest phase 1.
 constexpr int kChipFill = 256;
 int match_batch_threads() {
-    const char* s = std::getenv("ORBGPU_MATCH_THREADS");
-    const int v = s ? std::atoi(s) : kBatchThreads;
+    // read per launch: test_match_capacity.py::test_batch_block_sizes_and_level0_bound switches it in-process
+    const int v = env_now_int("ORBGPU_MATCH_THREADS", kBatchThreads);
     return v == 256 || v == 512 || v == 1024 ? v : kBatchThreads;
 }
 
-bool match_tiny_enabled() {
-    static const bool v = [] {  // read once per process (A/B runs set it per process)
-        const char* s = std::getenv("ORBGPU_MATCH_TINY");
-        return !s || std::atoi(s) != 0;
-    }();
-    return v;
-}
+// read once per process (A/B runs set it per process)
+bool match_tiny_enabled() { return ORB_ENV_ONCE_FLAG("ORBGPU_MATCH_TINY", true); }
 
 template <int kMaxK0, int kThreads>
 hipError_t launch_variant(int batch, int more, float minX, float maxX, float minY, float maxY,

@@ -1,5 +1,5 @@
-// orbgpu_internal.h -- geometry and buffer layout shared by the host driver
-// (orbgpu.cpp) and the HIP kernels.  Everything here is precomputed once per
+// orbgpu_internal.h -- geometry and buffer layout shared by the host code
+// (geometry.cpp, extractor.cpp) and the HIP kernels.  Everything here is precomputed once per
 // extractor on the host (it depends only on the frame size and the
 // ORBextractor parameters) and handed to kernels by value.
 #pragma once

@@ -5,7 +5,7 @@
 // Level l = resize(level l-1, INTER_LINEAR) with OpenCV-2.4's 8U fixed-point
 // arithmetic: Q11 horizontal taps (exact int), VResizeLinearVec_32s8u on
 // x < simd_end and FixedPtCast<int,uchar,22> on the tail.  The x/y tap tables
-// come from the host (orbgpu.cpp, build_resize_tables) exactly as resize()
+// come from the host (geometry.cpp, build_resize_tables) exactly as resize()
 // builds xofs/ialpha and yofs/ibeta.
 //
 // One block per frame, in ticks (plan: pyramid_plan.cpp).  Producer wave(s)
@@ -26,8 +26,8 @@
 // pass.
 // The vertical pass is four SDWA/op_sel instructions per pixel.
 #include <algorithm>
-#include <cstdlib>
 
+#include "host_common.h"
 #include "orbgpu_internal.h"
 #include "orbgpu_kernels.h"
 
@@ -614,10 +614,7 @@ void plan_pyramid_bands(Geom& g, const std::vector<int2>& ytab, std::vector<int4
     // overrides): a workgroup's level chain is latency bound, so more, smaller
     // bands finish sooner -- one 640x480 frame: 19.2 us at 32 bands, 16.3 us at
     // 64; 96 measured slower again (profiles/r06_notes_ab.txt r6k, r6m)
-    static const int nb_max = [] {
-        const char* s = std::getenv("ORBGPU_PYR_BANDS_MAX");
-        return s ? std::atoi(s) : 64;
-    }();
+    const int nb_max = ORB_ENV_ONCE_INT("ORBGPU_PYR_BANDS_MAX", 64);
     for (int nb : {128, 96, 64, 48, 32, 24, 16, 8}) {
         if (nb > nb_max) continue;
         bool ok = true;

@@ -29,13 +29,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstdint>
 
 #include "../../include/orbgpu.h"
 #include "orbgpu_internal.h"
 #include "stereo_kernels.h"
 #include "device_state.h"
+#include "host_common.h"
 #include "group_sum.h"
 
 namespace orbgpu {
@@ -336,14 +336,7 @@ size_t stereo_lds_bytes(int cap, int H) {
 // blocks per pair at most (ORBGPU_STEREO_SPLIT_MAX overrides): a single pair
 // (the stereo Frame's call) is dealt to this many blocks, whose waves then
 // take about 1200 / (16 S) left keypoints each
-int stereo_split_max() {
-    static const int v = [] {
-        const char* s = std::getenv("ORBGPU_STEREO_SPLIT_MAX");
-        const int x = s ? std::atoi(s) : 32;
-        return std::max(1, std::min(x, 256));
-    }();
-    return v;
-}
+int stereo_split_max() { return std::max(1, std::min(ORB_ENV_ONCE_INT("ORBGPU_STEREO_SPLIT_MAX", 32), 256)); }
 
 hipError_t launch_stereo(const StereoArgs& a, int npairs, hipStream_t stream) {
     if (npairs <= 0) return hipSuccess;

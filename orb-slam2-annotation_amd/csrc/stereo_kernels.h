@@ -1,4 +1,4 @@
-// stereo_kernels.h -- launch interface of stereo.hip (host driver: orbgpu.cpp).
+// stereo_kernels.h -- launch interface of stereo.hip (host entry points: stereo.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
