@@ -28,6 +28,9 @@ _LIB = None
 OK, ERR_ARG, ERR_HIP, ERR_CAPACITY, ERR_UNSUPPORTED, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 MATCH_CHECK_ORI = 1
 MATCH_ANNOTATED_HISTO = 2
+# orbgpu_rgbd.h: cvtColor codes and depth-map element types
+COLOR_RGB, COLOR_BGR, COLOR_RGBA, COLOR_BGRA = 0, 1, 2, 3
+DEPTH_U16, DEPTH_F32 = 0, 1
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -138,6 +141,10 @@ def lib() -> ctypes.CDLL:
         L.orbgpu_assign_features_to_grid_batch_device.argtypes = [i, GridBounds, vp, vp, i, vp, vp, vp]
         # orbgpu_stereo.h
         L.orbgpu_stereo_matches_batch_device.argtypes = [vp, vp, sz, sz, i, vp, vp, vp, i, f, f, vp, vp, vp]
+        # orbgpu_rgbd.h
+        L.orbgpu_gray_from_color_batch_device.argtypes = [vp, i, i, i, i, sz, sz, vp, sz, sz, vp]
+        L.orbgpu_stereo_from_rgbd_batch_device.argtypes = [vp, i, f, i, i, sz, sz, i, vp, vp, vp, i,
+                                                           ctypes.POINTER(Camera), f, vp, vp, vp, vp]
         # orbgpu_ransac.h
         L.orbgpu_srand.argtypes = [ctypes.c_uint]
         L.orbgpu_srand.restype = None
@@ -541,3 +548,65 @@ def assign_features_to_grid_batch(bounds: GridBounds, kps_un, counts, cell_start
                                                              kps_un.shape[1], _ptr(cell_start), _ptr(cell_items),
                                                              _stream_ptr(stream)),
            "assign_features_to_grid_batch_device")
+
+
+def color_channels(code: int) -> int:
+    """bytes per pixel of a COLOR_* code"""
+    return 4 if code in (COLOR_RGBA, COLOR_BGRA) else 3
+
+
+def gray_from_color_batch(color, code, gray, stream=None, width=None, row_step=None, frame_step=None):
+    """cvtColor(.., CV_{RGB,BGR,RGBA,BGRA}2GRAY) (Tracking.cpp:204-225) of B
+    colour frames in HBM.  color: uint8 (B, H, W, C) or (B, H, pitch_bytes)
+    device tensor (the latter with `width`, else pitch_bytes // channels);
+    gray: uint8 (B, H, pitch) device tensor, pitch >= width, whose bytes past
+    `width` are left alone.  Steps come from the tensors' strides; width,
+    row_step and frame_step (bytes) override those of `color`.  A gray tensor
+    with a 16-byte-aligned base and pitch is what extract_batch takes.
+    Asynchronous; color and gray must not overlap."""
+    ch = color_channels(code)
+    if color.dim() == 4:
+        if color.shape[3] != ch or color.stride(3) != 1 or color.stride(2) != ch:
+            raise ValueError(f"color: (B, H, W, {ch}) with interleaved channels expected for code {code}")
+        w = color.shape[2]
+    else:
+        if color.dim() != 3 or color.stride(2) != 1:
+            raise ValueError("color: (B, H, W, C) or (B, H, pitch_bytes) expected")
+        w = color.shape[2] // ch
+    w = int(width) if width is not None else w
+    if gray.dim() != 3 or gray.stride(2) != 1 or gray.shape[:2] != color.shape[:2]:
+        raise ValueError("gray: (B, H, pitch) with the batch and height of color expected")
+    B, H = color.shape[0], color.shape[1]
+    rs = row_step if row_step is not None else color.stride(1)
+    fs = frame_step if frame_step is not None else color.stride(0)
+    _check(lib().orbgpu_gray_from_color_batch_device(_ptr(color), int(code), w, H, B, rs, fs, _ptr(gray),
+                                                     gray.stride(1), gray.stride(0), _stream_ptr(stream)),
+           "orbgpu_gray_from_color_batch_device")
+
+
+def stereo_from_rgbd_batch(depth_maps, depth_factor, kps, kps_un, counts, cam: Camera, bf, uright, depth, x3dc=None,
+                           stream=None, width=None):
+    """Tracking.cpp:264-265 + Frame::ComputeStereoFromRGBD (Frame.cpp:751-773)
+    for B frames.  depth_maps: (B, H, pitch) device tensor, uint16 / int16
+    (read as uint16) or float32, pitch in elements (`width` columns of it,
+    default all); depth_factor: mDepthMapFactor after the reference's
+    inversion (TUM: 1/5000).  kps / kps_un: (B, cap, 7) raw and undistorted
+    keypoints; uright, depth: float32 (B, cap); x3dc: float32 (B, cap, 3) for
+    Frame::UnprojectStereo's camera-frame points, or None.  Slots past
+    counts[b] are not written.  Asynchronous."""
+    import torch
+    if depth_maps.dtype in (torch.uint16, torch.int16):
+        dtype = DEPTH_U16
+    elif depth_maps.dtype == torch.float32:
+        dtype = DEPTH_F32
+    else:
+        raise ValueError(f"depth_maps: uint16, int16 or float32 expected, not {depth_maps.dtype}")
+    if depth_maps.dim() != 3 or depth_maps.stride(2) != 1:
+        raise ValueError("depth_maps: (B, H, pitch) expected")
+    B, H = depth_maps.shape[0], depth_maps.shape[1]
+    w = int(width) if width is not None else depth_maps.shape[2]
+    es = depth_maps.element_size()
+    _check(lib().orbgpu_stereo_from_rgbd_batch_device(
+        _ptr(depth_maps), dtype, float(depth_factor), w, H, depth_maps.stride(1) * es, depth_maps.stride(0) * es, B,
+        _ptr(kps), _ptr(kps_un), _ptr(counts), kps.shape[1], ctypes.byref(cam), float(bf), _ptr(uright), _ptr(depth),
+        _ptr(x3dc) if x3dc is not None else None, _stream_ptr(stream)), "orbgpu_stereo_from_rgbd_batch_device")
