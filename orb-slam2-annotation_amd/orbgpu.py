@@ -145,6 +145,9 @@ def lib() -> ctypes.CDLL:
         L.orbgpu_gray_from_color_batch_device.argtypes = [vp, i, i, i, i, sz, sz, vp, sz, sz, vp]
         L.orbgpu_stereo_from_rgbd_batch_device.argtypes = [vp, i, f, i, i, sz, sz, i, vp, vp, vp, i,
                                                            ctypes.POINTER(Camera), f, vp, vp, vp, vp]
+        # orbgpu_poseopt.h
+        L.orbgpu_pose_optimization_batch_device.argtypes = [i, vp, i, vp, vp, vp, vp, vp, vp]
+        L.orbgpu_pose_optimization_batch.argtypes = [i, vp, i, vp, vp, vp, vp, vp]
         # orbgpu_ransac.h
         L.orbgpu_srand.argtypes = [ctypes.c_uint]
         L.orbgpu_srand.restype = None

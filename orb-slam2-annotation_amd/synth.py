@@ -865,3 +865,59 @@ def mappoint_scenario(n_points: int, seed: int, max_obs: int = 40, bad_frac: flo
     max_scale = np.full(n_points, sf[7], np.float32)
     return dict(offsets=off, desc=desc, valid=valid, pos=pos, obs_Ow=obs_Ow, ref_Ow=ref_Ow,
                 level_scale=level_scale, max_scale=max_scale)
+
+
+def _rodrigues(axis_angle):
+    a = np.asarray(axis_angle, np.float64)
+    th = np.linalg.norm(a)
+    if th == 0:
+        return np.eye(3)
+    k = a / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
+
+
+def pose_scene(n: int, seed: int, outliers: float = 0.2, stereo: float = 0.5, start_rot: float = 0.03,
+               start_t: float = 0.05, noise: float = 1.0, behind: int = 0):
+    """Observations of a frame for Optimizer::PoseOptimization: a random pose,
+    n MapPoints 2-12 m in front of the camera, keypoints at octaves 0-7
+    (inv_sigma2 = 1 / 1.2^(2 octave)) with Gaussian noise of `noise` pixels
+    times the level's scale factor, a fraction `outliers` of them 30-80 px
+    off, a fraction `stereo` with a right coordinate (the others uRight = -1),
+    and a start pose `start_rot` rad / `start_t` m from the truth.  `behind`
+    MapPoints are moved behind the camera (z < 0) with their observation kept.
+    Returns dict(Tcw0 (4x4), Tcw_true, Xw, obs (n, 3), inv_sigma2, K, bf,
+    outlier (injected), stereo) in float32."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, bf = 517.306408, 516.469215, 318.643040, 255.313989, 40.0
+    R = _rot(rng, 0.5)
+    t = rng.uniform(-1, 1, 3)
+    z = rng.uniform(2.0, 12.0, n)
+    u = rng.uniform(10, 630, n)
+    v = rng.uniform(10, 470, n)
+    Xc = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1)
+    Xw = (Xc - t) @ R
+    octave = rng.integers(0, 8, n)
+    scale = 1.2 ** octave
+    is_out = rng.uniform(size=n) < outliers
+    is_st = rng.uniform(size=n) < stereo
+    du = rng.normal(size=(n, 3)) * (noise * scale)[:, None]
+    ang = rng.uniform(0, 2 * np.pi, n)
+    off = rng.uniform(30, 80, n)
+    du[is_out, 0] += (off * np.cos(ang))[is_out]
+    du[is_out, 1] += (off * np.sin(ang))[is_out]
+    obs = np.stack([u + du[:, 0], v + du[:, 1], np.where(is_st, u - bf / z + du[:, 2], -1.0)], 1)
+    obs[is_st, 2] = np.maximum(obs[is_st, 2], 0.0)
+    for i in range(min(behind, n)):
+        Xc_b = Xc[i] * np.array([1.0, 1.0, -1.0])
+        Xw[i] = (Xc_b - t) @ R
+    dirs = rng.normal(size=(2, 3))
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    dR = _rodrigues(dirs[0] * start_rot)
+    T_true = np.eye(4)
+    T_true[:3, :3], T_true[:3, 3] = R, t
+    T0 = np.eye(4)
+    T0[:3, :3], T0[:3, 3] = dR @ R, dR @ t + dirs[1] * start_t
+    return {"Tcw0": T0.astype(np.float32), "Tcw_true": T_true.astype(np.float32), "Xw": Xw.astype(np.float32),
+            "obs": obs.astype(np.float32), "inv_sigma2": (1.0 / 1.2 ** (2.0 * octave)).astype(np.float32),
+            "K": (fx, fy, cx, cy), "bf": bf, "outlier": is_out, "stereo": is_st}
