@@ -333,6 +333,104 @@ __device__ __forceinline__ int arc_chunk(const CellTiles& T, int na, int base, i
     return nb1 + __popcll(m1);
 }
 
+// Packed 3-way max / min of f16 bit patterns whose second (S1) and third (S2)
+// sources may enter with their 16-bit halves exchanged: VOP3P's source-half
+// selects (op_sel picks the half feeding the low result, op_sel_hi the high
+// one), so the exchange costs no instruction.  The builtins cannot express
+// the selects, hence the asm.
+template <bool kMax, bool S1, bool S2>
+__device__ __forceinline__ uint32_t pk3_swz(uint32_t x, uint32_t y, uint32_t z) {
+    static_assert(S2 || !S1, "the networks below swap the third source, or the second and third");
+    uint32_t r;
+    if constexpr (kMax) {
+        if constexpr (S1)
+            asm("v_pk_maximum3_f16 %0, %1, %2, %3 op_sel:[0,1,1] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+        else if constexpr (S2)
+            asm("v_pk_maximum3_f16 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[1,1,0]" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+        else
+            asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+    } else {
+        if constexpr (S1)
+            asm("v_pk_minimum3_f16 %0, %1, %2, %3 op_sel:[0,1,1] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+        else if constexpr (S2)
+            asm("v_pk_minimum3_f16 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[1,1,0]" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+        else
+            asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+    }
+    return r;
+}
+
+// in[k], in[k + A], in[k + B] (A < B) -> out[k], k = 0 .. 7, of a 16-entry
+// circular sequence held as 8 registers: entry k in register k's low half,
+// entry k + 8 in its high half, so an index past 7 is the same register with
+// its halves exchanged, and out[k]'s high half is entry k + 8 of the result
+template <bool kMax, int A, int B, int K = 0>
+__device__ __forceinline__ void ring8_step(const uint32_t (&in)[8], uint32_t (&out)[8]) {
+    if constexpr (K < 8) {
+        out[K] = pk3_swz<kMax, (K + A >= 8), (K + B >= 8)>(in[K], in[(K + A) & 7], in[(K + B) & 7]);
+        ring8_step<kMax, A, B, K + 1>(in, out);
+    }
+}
+
+// The last chunk of a survivor list, 1 .. 64 entries (base + lane): one
+// survivor per lane, the same arc strength as arc_chunk in half its min / max
+// instructions.  Register k of 8 holds ring position k in its low half and
+// k + 8 in its high half (f16 denormal bit patterns as above), so the 16
+// circular 3-runs are 8 packed ops (run k + 8 is the high half of run k's
+// register), the 16 9-arcs H9[k] = op3(H3[k], H3[k + 3], H3[k + 6]) 8 more, and
+// the reduction over the arcs 4 three-input ops and one against the
+// register's own exchanged halves: 21 ops for max-of-min and 21 for
+// min-of-max, against 40 + 40.  One append (list order), so the corner list
+// stays row-major; it writes lb below nb + 64 <= base + 64, i.e. below the
+// entries this and the earlier chunks have read (no later chunk reads).
+template <int P>
+__device__ __forceinline__ int arc_chunk_half(const CellTiles& T, int na, int base, int t, int lane, int nb) {
+    const int j = base + lane;
+    const int off = T.la[min(j, na - 1)];  // clamped: a real pixel
+    const uint8_t* p = T.win - (3 * P + 3) + off;  // the circle's top-left corner, as in arc_chunk
+    const int ring_dx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+    const int ring_dy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
+    auto at = [&](int k) { return (uint32_t)p[(ring_dy[k] + 3) * P + ring_dx[k] + 3]; };
+    uint32_t r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = at(k) | (at(k + 8) << 16);  // (one v_lshl_or; no D16 loads: see ring_pairs)
+    const int v = p[3 * P + 3];
+    uint32_t hi3[8], lo3[8], hi9[8], lo9[8];
+    ring8_step<true, 1, 2>(r, hi3);
+    ring8_step<false, 1, 2>(r, lo3);
+    ring8_step<true, 3, 6>(hi3, hi9);
+    ring8_step<false, 3, 6>(lo3, lo9);
+    uint32_t A = pk3_swz<false, false, false>(hi9[0], hi9[1], hi9[2]), B = pk3_swz<true, false, false>(lo9[0], lo9[1], lo9[2]);
+    A = pk3_swz<false, false, false>(A, hi9[3], hi9[4]);
+    B = pk3_swz<true, false, false>(B, lo9[3], lo9[4]);
+    A = pk3_swz<false, false, false>(A, hi9[5], hi9[6]);
+    B = pk3_swz<true, false, false>(B, lo9[5], lo9[6]);
+    A = pk3_swz<false, false, false>(A, hi9[7], hi9[7]);
+    B = pk3_swz<true, false, false>(B, lo9[7], lo9[7]);
+    A = pk3_swz<false, true, true>(A, A, A);  // low half: the min over all 16 arcs
+    B = pk3_swz<true, true, true>(B, B, B);
+    const int sc = max(v - (int)(A & 0xFFFFu), (int)(B & 0xFFFFu) - v);  // arc strength (cornerScore + 1)
+    const bool c = (j < na) & (sc > t);
+    const unsigned long long m = __ballot(c);
+    const int pos = nb + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (c) {
+        T.sc[off] = (uint8_t)sc;
+        T.lb[pos] = (uint16_t)off;
+    }
+    return nb + __popcll(m);
+}
+
+// The arc pass over list entries [nb, na): full chunks while 65 or more
+// entries remain, then one half chunk for a tail of 1 .. 64; corners are
+// compacted in place from nb on, behind the survivors being read.
+template <int P>
+__device__ __forceinline__ int arc_pass(const CellTiles& T, int na, int t, int lane, int nb) {
+    int base = nb;
+    for (; na - base > 64; base += 128) nb = arc_chunk<P>(T, na, base, t, lane, nb);
+    if (base < na) nb = arc_chunk_half<P>(T, na, base, t, lane, nb);
+    return nb;
+}
+
 // FAST at threshold t on the cell's detection region: returns the number
 // of corners, their tile offsets in lb[] (row-major) and scores in sc[].
 // Stages are separated by wave compaction so each runs on dense lanes:
@@ -351,10 +449,10 @@ __device__ int fast_corners(const CellTiles& T, int dw, int dh, int ox, int t, i
         stamp[1] = (unsigned long long)na;
     }
 #endif
-    // survivors -> corners, two per lane (arc_chunk), compacted in place
-    // behind the survivors being read
-    int nb = 0;
-    for (int base = 0; base < na; base += 128) nb = arc_chunk<P>(T, na, base, t, lane, nb);
+    // survivors -> corners, two per lane (arc_chunk) and one per lane for a
+    // tail of <= 64 (arc_chunk_half), compacted in place behind the survivors
+    // being read
+    const int nb = arc_pass<P>(T, na, t, lane, 0);
     wave_sync();
     return nb;
 }
@@ -424,10 +522,8 @@ __device__ int fast_cell_banded(const CellTiles& T, int dw, int dh, int ox, int 
                        : dw > 32              ? compass_pass<P, 64, true>(T, dw, dh, ox, t, lane, row, nb, &row_end)
                                               : compass_pass<P, 32, true>(T, dw, dh, ox, t, lane, row, nb, &row_end);
         wave_sync();
-        int nc = nb;
-        for (int base = nb; base < na; base += 128) nc = arc_chunk<P>(T, na, base, t, lane, nc);
+        nb = arc_pass<P>(T, na, t, lane, nb);
         wave_sync();
-        nb = nc;
         row = row_end;
         // corners to emit now: all of them at the end, else those above row - 1
         int k = nb;
