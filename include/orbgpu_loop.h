@@ -18,7 +18,10 @@
  * hot path) and stops at the first candidate whose optimisation keeps >= 20
  * inliers.  Here that verification is taken to pass, so a query ends at the
  * first RANSAC success in the reference's candidate order -- the result the
- * caller then verifies.  Everything up to that point is the reference's:
+ * caller then verifies.  The verification's optimisation is now on the device
+ * too: orbgpu_optimize_sim3_batch (orbgpu_sim3opt.h) is OptimizeSim3, so the
+ * caller can run :358-398 on the returned Sim3 without g2o; it is a separate
+ * call, not part of this one.  Everything up to that point is the reference's:
  * the same candidates discarded, the same hypotheses drawn from the same
  * glibc rand() stream in the same order (iterate(5) per candidate per round),
  * the same acceptance.

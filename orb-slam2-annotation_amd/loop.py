@@ -9,7 +9,8 @@ include/orbgpu_loop.h (csrc/loop.hip) and include/orbgpu_bow.h.
   every candidate (:311), the Sim3Solver constructors of the candidates with
   >= 20 matches (:314-324), then the round-robin iterate(5) RANSAC until the
   first candidate returns a Sim3 (:339-356; the SearchBySim3/OptimizeSim3
-  verification that follows is outside the hot path and taken to pass).
+  verification that follows is outside the hot path and taken to pass; its
+  optimisation, OptimizeSim3, is a separate call: sim3opt.optimize_sim3_batch).
 
 Everything runs on the GPU in four launches per step (SearchByBoW batch,
 Sim3Solver set-up, ComputeSim3); there is no host fallback.

@@ -148,6 +148,9 @@ def lib() -> ctypes.CDLL:
         # orbgpu_poseopt.h
         L.orbgpu_pose_optimization_batch_device.argtypes = [i, vp, i, vp, vp, vp, vp, vp, vp]
         L.orbgpu_pose_optimization_batch.argtypes = [i, vp, i, vp, vp, vp, vp, vp]
+        # orbgpu_sim3opt.h
+        L.orbgpu_optimize_sim3_batch_device.argtypes = [i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbgpu_optimize_sim3_batch.argtypes = [i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
         # orbgpu_ransac.h
         L.orbgpu_srand.argtypes = [ctypes.c_uint]
         L.orbgpu_srand.restype = None

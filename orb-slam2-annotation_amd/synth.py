@@ -921,3 +921,55 @@ def pose_scene(n: int, seed: int, outliers: float = 0.2, stereo: float = 0.5, st
     return {"Tcw0": T0.astype(np.float32), "Tcw_true": T_true.astype(np.float32), "Xw": Xw.astype(np.float32),
             "obs": obs.astype(np.float32), "inv_sigma2": (1.0 / 1.2 ** (2.0 * octave)).astype(np.float32),
             "K": (fx, fy, cx, cy), "bf": bf, "outlier": is_out, "stereo": is_st}
+
+
+def sim3opt_scene(n: int, seed: int, outliers: float = 0.2, fix_scale: bool = False, start_rot: float = 0.02,
+                  start_t: float = 0.05, start_s: float = 1.03, noise: float = 1.0, behind: int = 0,
+                  th2: float = 10.0):
+    """Correspondences of a loop candidate for Optimizer::OptimizeSim3: a random
+    S12 = (R, t, s) (s = 1 under fix_scale), n MapPoints 2-12 m in front of
+    keyframe 2 with P1c = s R P2c + t, keypoints in both keyframes at octaves
+    0-7 (inv_sigma2 = 1 / 1.2^(2 octave)) with Gaussian noise of `noise` pixels
+    times the level's scale factor, a fraction `outliers` of the keyframe-1
+    keypoints 30-80 px off, and a start `start_rot` rad / `start_t` m / a
+    factor `start_s` in scale (1 under fix_scale) from the truth.  `behind`
+    MapPoints lie behind keyframe 1 (P1c.z < 0) with their keypoints kept.
+    Returns dict(q12 (x, y, z, w), t12, s12 in float64; P1c, P2c (n, 3), obs1,
+    obs2 (n, 2), inv_sigma2_1, inv_sigma2_2 in float32; K1, K2, th2,
+    fix_scale, outlier (injected), R_true, t_true, s_true)."""
+    rng = np.random.default_rng(seed)
+    K = np.array([517.306408, 516.469215, 318.643040, 255.313989])
+    R = _rot(rng, 0.2)
+    t = rng.uniform(-0.5, 0.5, 3)
+    s = 1.0 if fix_scale else float(rng.uniform(0.7, 1.4))
+    z = rng.uniform(2.0, 12.0, n)
+    u = rng.uniform(10, 630, n)
+    v = rng.uniform(10, 470, n)
+    P2 = np.stack([(u - K[2]) / K[0] * z, (v - K[3]) / K[1] * z, z], 1)
+    P1 = s * (P2 @ R.T) + t
+    oct1, oct2 = rng.integers(0, 8, n), rng.integers(0, 8, n)
+    is_out = rng.uniform(size=n) < outliers
+    d1 = rng.normal(size=(n, 2)) * (noise * 1.2 ** oct1)[:, None]
+    d2 = rng.normal(size=(n, 2)) * (noise * 1.2 ** oct2)[:, None]
+    ang = rng.uniform(0, 2 * np.pi, n)
+    off = rng.uniform(30, 80, n)
+    d1[is_out, 0] += (off * np.cos(ang))[is_out]
+    d1[is_out, 1] += (off * np.sin(ang))[is_out]
+    obs1 = P1[:, :2] / P1[:, 2:3] * K[:2] + K[2:] + d1
+    obs2 = P2[:, :2] / P2[:, 2:3] * K[:2] + K[2:] + d2
+    for i in range(min(behind, n)):
+        P1[i, 2] = -P1[i, 2]
+        P2[i] = ((P1[i] - t) @ R) / s
+    dirs = rng.normal(size=(2, 3))
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    dR = _rodrigues(dirs[0] * start_rot)
+    R0, t0 = dR @ R, dR @ t + dirs[1] * start_t
+    s0 = s if fix_scale else s * start_s
+    w = np.sqrt(max(0.0, 1.0 + R0[0, 0] + R0[1, 1] + R0[2, 2])) / 2.0  # max rotation 0.6 rad + start: w > 0.5
+    q = np.array([(R0[2, 1] - R0[1, 2]) / (4 * w), (R0[0, 2] - R0[2, 0]) / (4 * w), (R0[1, 0] - R0[0, 1]) / (4 * w), w])
+    q /= np.linalg.norm(q)
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    return {"q12": q, "t12": t0.astype(np.float64), "s12": float(s0), "P1c": f32(P1), "P2c": f32(P2),
+            "obs1": f32(obs1), "obs2": f32(obs2), "inv_sigma2_1": f32(1.0 / 1.2 ** (2.0 * oct1)),
+            "inv_sigma2_2": f32(1.0 / 1.2 ** (2.0 * oct2)), "K1": tuple(K), "K2": tuple(K), "th2": float(th2),
+            "fix_scale": bool(fix_scale), "outlier": is_out, "R_true": R, "t_true": t, "s_true": s}
