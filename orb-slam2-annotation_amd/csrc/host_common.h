@@ -28,6 +28,27 @@ int check_device();
 // ORBGPU_ERR_NO_DEVICE when no device is visible
 int validate_device(int device);
 
+// The argument checks of a batch entry point whose jobs own ranges of shared per-item arrays
+// (poseopt.hip, sim3opt.hip), made before the device is looked at; no pointer is dereferenced.
+// `total_name` and `noun` are the entry point's words for the arrays' length and their items.
+inline int check_batch_args(int batch, int total, const char* total_name, bool jobs_and_results, bool arrays,
+                            const char* noun) {
+    if (batch < 0 || total < 0) return fail(ORBGPU_ERR_ARG, std::string("negative batch or ") + total_name);
+    if (batch > 0 && !jobs_and_results) return fail(ORBGPU_ERR_ARG, "null jobs or results");
+    if (batch > 0 && total > 0 && !arrays) return fail(ORBGPU_ERR_ARG, std::string("null ") + noun + " array");
+    return ORBGPU_OK;
+}
+// every job's [offset, offset + n) lies in [0, total); `jobs` is host memory
+template <class Job>
+int check_job_ranges(int batch, const Job* jobs, int total) {
+    for (int b = 0; b < batch; ++b) {
+        const Job& j = jobs[b];
+        if (j.n < 0 || j.offset < 0 || (long long)j.offset + j.n > (long long)total)
+            return fail(ORBGPU_ERR_ARG, "job " + std::to_string(b) + " is out of the array bounds");
+    }
+    return ORBGPU_OK;
+}
+
 // Makes `device` the calling thread's current HIP device for the scope and
 // restores the previous one (device < 0: leaves the thread's device alone).
 // Every entry point that takes an extractor runs under the extractor's device,

@@ -7,15 +7,18 @@
 // (core/robust_kernel_impl.cpp:64-91), the two Sim3 projection edges
 // (types/types_seven_dof_expmap.h:61-90, 131-172) and Sim3 (types/sim3.h).
 // tests/sim3opt_ref.py is the same arithmetic, expression for expression.
+// The LM state machine, the 7x7 solve, Huber, the quaternion algebra, the
+// workgroup sum and the matrix write-out are lm_device.h's, shared with
+// poseopt.hip; this file adds the Sim3 update (sim3opt_device.h), the two
+// edges with their numeric Jacobians and the two optimisations with their checks.
 //
 // One workgroup per job, one launch for both optimisations and both checks.
 // Correspondence i of a job belongs to lane i % T for the whole call: the lane
 // reads it (from LDS when the job has at most kCap correspondences, else from
 // HBM/L2), keeps its flag and adds its two edges' terms to 36 private doubles
 // -- the 28 upper entries of H, the 7 of b and the robust chi2.  The sums are
-// reduced in a fixed order: DPP row sums (group_sum.h), one LDS row per 16
-// lanes, then lanes 0..35 add the rows in order.  No floating-point atomics: a
-// job's bits do not depend on its neighbours, its block index or the call.
+// reduced in a fixed order (lm::block_sum): a job's bits do not depend on its
+// neighbours, its block index or the call.
 //
 // Two kinds of pass.  A *build* pass is g2o's computeActiveErrors +
 // buildSystem at the estimate: lanes 0..14 first leave the estimate, its 14
@@ -29,87 +32,46 @@
 // convergence most trials are rejected (up to ten per iteration), so this is
 // the cheaper choice; the bits are the same either way.
 //
-// After each pass lane 0 advances the LM state machine in LDS (accept /
-// reject, lambda, the stop rules, the next 7x7 solve and Sim3(x) * estimate)
-// and leaves `mode` and `done` there; every lane reads those words after the
+// After each pass lane 0 advances the LM state machine in LDS (lm::step: accept /
+// reject, lambda, the stop rules, the next solve and Sim3(x) * estimate) and
+// leaves `phase` and `done` there; every lane reads those words after the
 // barrier, so no lane ever decides from a sum of its own.  The loop bound,
 // 10 x (1 + 10) passes, is the reference's 10 iterations of 10 trials; the
 // kernel ends on any input.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <string>
 
 #include "../../include/orbgpu_sim3opt.h"
-#include "group_sum.h"
 #include "host_common.h"
 #include "host_ctx.h"
 #include "sim3opt_device.h"
 
 namespace {
 
+namespace lm = orbgpu::lm;
 using orbgpu::sim3opt::Sim3;
+using Lm = lm::State<7, Sim3>;
 
 constexpr int kCap = 768;    // correspondences of a job kept in LDS (12 floats and a flag byte each)
-constexpr int kVals = 36;    // H (28), b (7), robust chi2
+constexpr int kVals = Lm::kVals;  // H (28), b (7), robust chi2
 constexpr int kStates = 15;  // the estimate and oplus(+-1e-9 e_d), d = 0..6
 constexpr int kMaxPasses = 110;
 constexpr int kThreads = 256;
 constexpr double kDelta = 1e-9;                  // base_binary_edge.hpp:147
 constexpr double kScalar = 1.0 / (2 * kDelta);   // :148
 
-enum { kPhaseInit = 0, kPhaseRebuild = 1, kPhaseTrial = 2 };
-enum { kModeBuild = 0, kModeTrial = 1 };
-
 // the job's state in LDS; written by lane 0 between barriers, read by all
 struct Ctl {
-    double tot[kVals];        // the last pass' sums
-    double H[28], b[7], chi;  // system and robust chi2 at `est`
-    double L[28];             // Cholesky factor, lower triangle row by row
-    double x[7], y[7];
-    Sim3 est, trial;
-    double lambda, ni, ini_chi;
+    Lm lm;
+    double L[28], y[7];       // the solve's Cholesky factor and forward substitution
     double delta, dsqr, th2;  // Huber's (float)sqrt(th2), its float square; th2
     double K1[4], K2[4];
-    int n, offset, valid, fix_scale;
-    int phase, mode, ok, iter, max_iter, qmax, stop_bad, rejected, done, n_bad;
+    int n, offset, valid, fix_scale, n_bad;
     int lm_iterations[2], lm_rejected[2];
 };
-
-// index of H(j, k), j <= k, among the 28 upper entries (row by row)
-__host__ __device__ constexpr int upper_index(int j, int k) { return j * 7 - j * (j - 1) / 2 + (k - j); }
-__device__ inline int lower_index(int i, int j) { return i * (i + 1) / 2 + j; }
-
-// (H + lambda I) x = b by Cholesky, in LDS (lane 0; rolled loops, run-time indices); false when a
-// pivot is not positive
-__device__ bool solve7(Ctl& c, double lambda) {
-    for (int j = 0; j < 7; ++j) {
-        double s = c.H[upper_index(j, j)] + lambda;
-        for (int k = 0; k < j; ++k) s -= c.L[lower_index(j, k)] * c.L[lower_index(j, k)];
-        if (!(s > 0)) return false;
-        const double d = __dsqrt_rn(s);
-        c.L[lower_index(j, j)] = d;
-        for (int i = j + 1; i < 7; ++i) {
-            double r = c.H[upper_index(j, i)];
-            for (int k = 0; k < j; ++k) r -= c.L[lower_index(i, k)] * c.L[lower_index(j, k)];
-            c.L[lower_index(i, j)] = r / d;
-        }
-    }
-    for (int i = 0; i < 7; ++i) {
-        double s = c.b[i];
-        for (int k = 0; k < i; ++k) s -= c.L[lower_index(i, k)] * c.y[k];
-        c.y[i] = s / c.L[lower_index(i, i)];
-    }
-    for (int i = 6; i >= 0; --i) {
-        double s = c.y[i];
-        for (int k = i + 1; k < 7; ++k) s -= c.L[lower_index(k, i)] * c.x[k];
-        c.x[i] = s / c.L[lower_index(i, i)];
-    }
-    return true;
-}
 
 // VertexSim3Expmap::oplusImpl of u on est
 __device__ inline void oplus(const Sim3& est, double (&u)[7], bool fix_scale, Sim3& out) {
@@ -117,89 +79,6 @@ __device__ inline void oplus(const Sim3& est, double (&u)[7], bool fix_scale, Si
     Sim3 e;
     orbgpu::sim3opt::sim3_exp(u, e);
     orbgpu::sim3opt::sim3_mul(e, est, out);
-}
-
-// the next trial: solve at the current lambda, trial = Sim3(x) * est (a failed solve: x = 0,
-// trial = est).  oplusImpl zeroes the solver's own x[6] under fix_scale, so computeScale sees 0.
-__device__ void next_trial(Ctl& c) {
-    const bool ok = solve7(c, c.lambda);
-    if (ok) {
-        double u[7];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) u[i] = c.x[i];
-        const Sim3 est = c.est;
-        Sim3 trial;
-        oplus(est, u, c.fix_scale != 0, trial);
-        c.trial = trial;
-        c.x[6] = u[6];
-    } else {
-        for (int i = 0; i < 7; ++i) c.x[i] = 0.0;
-        c.trial = c.est;
-    }
-    c.ok = ok ? 1 : 0;
-    c.mode = kModeTrial;
-    c.phase = kPhaseTrial;
-}
-
-// OptimizationAlgorithmLevenberg::solve, one pass at a time
-__device__ void lm_step(Ctl& c) {
-    if (c.phase != kPhaseTrial) {  // a build pass at c.est: the iteration's system and chi2
-        for (int i = 0; i < 28; ++i) c.H[i] = c.tot[i];
-        for (int i = 0; i < 7; ++i) c.b[i] = c.tot[28 + i];
-        c.chi = c.tot[35];
-        if (c.phase == kPhaseInit) {
-            double max_diag = 0.0;
-            for (int j = 0; j < 7; ++j) {  // std::max(fabs(h), maxDiagonal)
-                const double a = fabs(c.H[upper_index(j, j)]);
-                max_diag = a < max_diag ? max_diag : a;
-            }
-            c.lambda = 1e-5 * max_diag;
-            c.ni = 2.0;
-            c.stop_bad = 0;
-        }
-        c.iter += 1;
-        c.ini_chi = c.chi;
-        c.qmax = 0;
-        next_trial(c);
-        return;
-    }
-    const double tmp_chi = c.ok ? c.tot[35] : DBL_MAX;
-    double scale = 0.0;
-    for (int j = 0; j < 7; ++j) scale += c.x[j] * (c.lambda * c.x[j] + c.b[j]);
-    scale += 1e-3;
-    const double rho = (c.chi - tmp_chi) / scale;
-    if (rho > 0 && isfinite(tmp_chi)) {
-        const double t3 = 2.0 * rho - 1.0;
-        double alpha = 1.0 - (t3 * t3) * t3;
-        alpha = alpha < 2.0 / 3.0 ? alpha : 2.0 / 3.0;
-        c.lambda *= (1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0);
-        c.ni = 2.0;
-        c.chi = tmp_chi;
-        c.est = c.trial;
-    } else {
-        c.lambda *= c.ni;
-        c.ni *= 2.0;
-        c.rejected += 1;
-    }
-    c.qmax += 1;
-    if (rho < 0 && c.qmax < 10) {
-        next_trial(c);
-        return;
-    }
-    if (c.qmax == 10 || rho == 0) {
-        c.done = 1;
-        return;
-    }
-    if ((c.ini_chi - c.chi) * 1e3 < c.ini_chi)
-        c.stop_bad += 1;
-    else
-        c.stop_bad = 0;
-    if (c.stop_bad >= 3 || c.iter >= c.max_iter) {
-        c.done = 1;
-        return;
-    }
-    c.mode = kModeBuild;  // the next iteration's computeActiveErrors + buildSystem at c.est
-    c.phase = kPhaseRebuild;
 }
 
 // ------------------------------------------------------------------ the edges (every lane)
@@ -214,23 +93,13 @@ __device__ __forceinline__ void project_error(const Sim3& S, const double (&P)[3
                                               const double* K, double& e0, double& e1) {
     const double q[4] = {S.q[0], S.q[1], S.q[2], S.q[3]};
     double r0, r1, r2;
-    orbgpu::sim3opt::quat_rotate(q, P[0], P[1], P[2], r0, r1, r2);
+    lm::quat_rotate(q, P[0], P[1], P[2], r0, r1, r2);
     const double s = S.s;
     const double x = s * r0 + S.t[0];
     const double y = s * r1 + S.t[1];
     const double z = s * r2 + S.t[2];
     e0 = o[0] - ((x / z) * K[0] + K[2]);
     e1 = o[1] - ((y / z) * K[1] + K[3]);
-}
-
-// RobustKernelHuber::robustify
-__device__ __forceinline__ void huber(double chi2, double delta, double dsqr, double& rho0, double& rho1) {
-    rho0 = chi2, rho1 = 1.0;
-    if (!(chi2 <= dsqr)) {
-        const double sq = __dsqrt_rn(chi2);
-        rho0 = (2.0 * sq) * delta - dsqr;
-        rho1 = delta / sq;
-    }
 }
 
 // one edge's linearizeOplus + constructQuadraticForm: `states` are the 15 estimates the edge maps
@@ -242,7 +111,7 @@ __device__ __forceinline__ void add_edge(double (&acc)[kVals], const Sim3* state
     project_error(states[0], P, o, K, e[0], e[1]);
     const double chi2 = e[0] * (w * e[0]) + e[1] * (w * e[1]);
     double rho0, rho1;
-    huber(chi2, delta, dsqr, rho0, rho1);
+    lm::huber(chi2, delta, dsqr, rho0, rho1);
     double J[7][2];
 #pragma unroll
     for (int d = 0; d < 7; ++d) {
@@ -264,7 +133,7 @@ __device__ __forceinline__ void add_edge(double (&acc)[kVals], const Sim3* state
         __builtin_amdgcn_sched_barrier(0);  // one row of H at a time: the 28 products are independent
         const double wj0 = W * J[j][0], wj1 = W * J[j][1];
 #pragma unroll
-        for (int k = j; k < 7; ++k) acc[upper_index(j, k)] += wj0 * J[k][0] + wj1 * J[k][1];
+        for (int k = j; k < 7; ++k) acc[lm::upper_index<7>(j, k)] += wj0 * J[k][0] + wj1 * J[k][1];
         acc[28 + j] += J[j][0] * omr[0] + J[j][1] * omr[1];
     }
     acc[35] += rho0;
@@ -334,13 +203,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
         ctl.offset = valid ? offset : 0;
         ctl.fix_scale = job->fix_scale;
         for (int k = 0; k < 4; ++k) {
-            ctl.est.q[k] = job->q12[k];
+            ctl.lm.est.q[k] = job->q12[k];
             ctl.K1[k] = (double)job->K1[k];
             ctl.K2[k] = (double)job->K2[k];
         }
-        for (int k = 0; k < 3; ++k) ctl.est.t[k] = job->t12[k];
-        ctl.est.s = job->s12;
-        ctl.trial = ctl.est;
+        for (int k = 0; k < 3; ++k) ctl.lm.est.t[k] = job->t12[k];
+        ctl.lm.est.s = job->s12;
+        ctl.lm.trial = ctl.lm.est;
         const float th2 = job->th2;
         const float delta = (float)__dsqrt_rn((double)th2);  // const float deltaHuber = sqrt(th2)
         ctl.th2 = (double)th2;
@@ -381,36 +250,34 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     // lane i % T alone touches correspondence i, its LDS copy and its flag: no barrier is needed for them
 
     const Src src = {P1c, P2c, obs1, obs2, w1, w2, base, on_chip};
+    // the LM step's update; fix_scale by value: a reference would give it an address in scratch
+    const auto update = [fix_scale](const Sim3& est, double (&u)[7], Sim3& out) { oplus(est, u, fix_scale, out); };
 
     int rounds = 0, n_bad_first = 0, n_in = 0;               // uniform: read from ctl after barriers
     for (int round = 0; round < 2 && n > 0; ++round) {
         if (tid == 0) {
             // initializeOptimization + optimize(): lambda, ni and the stop counter start afresh at
             // iteration 0, the estimate is the vertex' (the first optimisation's result in round 1)
-            ctl.trial = ctl.est;
-            ctl.phase = kPhaseInit;
-            ctl.mode = kModeBuild;
-            ctl.max_iter = round == 0 ? 5 : (n_bad_first > 0 ? 10 : 5);
-            ctl.iter = 0, ctl.qmax = 0, ctl.rejected = 0, ctl.done = 0, ctl.ok = 1;
+            lm::start(ctl.lm, round == 0 ? 5 : (n_bad_first > 0 ? 10 : 5));
             ctl.n_bad = 0;
         }
         __syncthreads();
 
         for (int pass = 0; pass < kMaxPasses; ++pass) {
-            const bool build = ctl.mode == kModeBuild;
+            const bool build = ctl.lm.phase != lm::kTrial;
             if (tid < (build ? kStates : 1)) {
                 Sim3 S;
                 if (!build) {
-                    S = ctl.trial;
+                    S = ctl.lm.trial;
                 } else if (tid == 0) {
-                    S = ctl.est;
+                    S = ctl.lm.est;
                 } else {
                     const int d = (tid - 1) >> 1;
                     const double step = (tid & 1) ? kDelta : -kDelta;
                     double u[7];
 #pragma unroll
                     for (int k = 0; k < 7; ++k) u[k] = k == d ? step : 0.0;
-                    const Sim3 est = ctl.est;
+                    const Sim3 est = ctl.lm.est;
                     oplus(est, u, fix_scale, S);
                 }
                 Sim3 Sinv;
@@ -439,34 +306,17 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
                     for (int edge = 0; edge < 2; ++edge) {
                         double rho0, rho1;
                         const EdgeIn e = load_edge(s_corr, src, i, edge);
-                        huber(edge_chi2(e, edge ? s_Sinv[0] : s_S[0], edge ? K2 : K1), delta, dsqr, rho0, rho1);
+                        lm::huber(edge_chi2(e, edge ? s_Sinv[0] : s_S[0], edge ? K2 : K1), delta, dsqr, rho0, rho1);
                         acc[35] += rho0;
                     }
                 }
             }
-            // fixed-order sum over the workgroup: 16-lane rows on DPP, rows through LDS
-            if (build) {
-#pragma unroll
-                for (int v = 0; v < kVals - 1; ++v) acc[v] = orbgpu::row16_sum(acc[v]);
-            }
-            acc[35] = orbgpu::row16_sum(acc[35]);
-            if ((tid & 15) == 0) {
-                if (build) {
-#pragma unroll
-                    for (int v = 0; v < kVals - 1; ++v) s_part[tid >> 4][v] = acc[v];
-                }
-                s_part[tid >> 4][35] = acc[35];
-            }
+            const double sum = lm::block_sum<T>(acc, s_part, build ? 0 : kVals - 1, kVals - 1);
+            if (tid < kVals && (build || tid == kVals - 1)) ctl.lm.tot[tid] = sum;
             __syncthreads();
-            if (tid < kVals && (build || tid == 35)) {
-                double sum = s_part[0][tid];
-                for (int r = 1; r < T / 16; ++r) sum += s_part[r][tid];
-                ctl.tot[tid] = sum;
-            }
+            if (tid == 0) lm::step<false>(ctl.lm, ctl.L, ctl.y, update);
             __syncthreads();
-            if (tid == 0) lm_step(ctl);
-            __syncthreads();
-            if (ctl.done) break;
+            if (ctl.lm.done) break;
         }
 
         // the check (Optimizer.cpp:1377-1394, :1411-1425): chi2() of an edge still in the graph is
@@ -490,8 +340,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
         }
         __syncthreads();
         if (tid == 0) {
-            ctl.lm_iterations[round] = ctl.iter;
-            ctl.lm_rejected[round] = ctl.rejected;
+            ctl.lm_iterations[round] = ctl.lm.iter;
+            ctl.lm_rejected[round] = ctl.lm.rejected;
         }
         const int n_bad = __builtin_amdgcn_readfirstlane(ctl.n_bad);
         rounds = round + 1;
@@ -516,26 +366,15 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
         for (int k = 0; k < 2; ++k) r->lm_iterations[k] = ctl.lm_iterations[k], r->lm_rejected[k] = ctl.lm_rejected[k];
         r->pad = 0;
         if (rounds == 2) {
-            for (int k = 0; k < 4; ++k) r->q12[k] = ctl.est.q[k];
-            for (int k = 0; k < 3; ++k) r->t12[k] = ctl.est.t[k];
-            r->s12 = ctl.est.s;
+            for (int k = 0; k < 4; ++k) r->q12[k] = ctl.lm.est.q[k];
+            for (int k = 0; k < 3; ++k) r->t12[k] = ctl.lm.est.t[k];
+            r->s12 = ctl.lm.est.s;
         } else {
             for (int k = 0; k < 4; ++k) r->q12[k] = job->q12[k];
             for (int k = 0; k < 3; ++k) r->t12[k] = job->t12[k];
             r->s12 = job->s12;
         }
-        // Converter::toCvMat(g2o::Sim3): s * toRotationMatrix(), translation
-        const double x = r->q12[0], y = r->q12[1], z = r->q12[2], w = r->q12[3], s = r->s12;
-        const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-        const double twx = tx * w, twy = ty * w, twz = tz * w;
-        const double txx = tx * x, txy = ty * x, txz = tz * x;
-        const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-        float* T16 = r->T12;
-        T16[0] = (float)(s * (1.0 - (tyy + tzz))), T16[1] = (float)(s * (txy - twz)), T16[2] = (float)(s * (txz + twy));
-        T16[4] = (float)(s * (txy + twz)), T16[5] = (float)(s * (1.0 - (txx + tzz))), T16[6] = (float)(s * (tyz - twx));
-        T16[8] = (float)(s * (txz - twy)), T16[9] = (float)(s * (tyz + twx)), T16[10] = (float)(s * (1.0 - (txx + tyy)));
-        T16[3] = (float)r->t12[0], T16[7] = (float)r->t12[1], T16[11] = (float)r->t12[2];
-        T16[12] = 0.0f, T16[13] = 0.0f, T16[14] = 0.0f, T16[15] = 1.0f;
+        lm::write_T16(r->q12, r->t12, r->s12, r->T12);  // Converter::toCvMat(g2o::Sim3)
     }
 }
 
@@ -545,18 +384,7 @@ void empty_result(const orbgpu_sim3opt_job& j, orbgpu_sim3opt_result& r) {
     std::memcpy(r.q12, j.q12, sizeof(j.q12));
     std::memcpy(r.t12, j.t12, sizeof(j.t12));
     std::memcpy(&r.s12, &j.s12, sizeof(j.s12));
-    const double x = j.q12[0], y = j.q12[1], z = j.q12[2], w = j.q12[3], s = j.s12;
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    const double R[9] = {1.0 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.0 - (txx + tzz),
-                         tyz - twx,         txz - twy, tyz + twx, 1.0 - (txx + tyy)};
-    for (int i = 0; i < 3; ++i) {
-        for (int k = 0; k < 3; ++k) r.T12[4 * i + k] = (float)(s * R[3 * i + k]);
-        r.T12[4 * i + 3] = (float)j.t12[i];
-    }
-    r.T12[15] = 1.0f;
+    lm::write_T16(j.q12, j.t12, j.s12, r.T12);
 }
 
 }  // namespace
@@ -566,11 +394,10 @@ extern "C" int orbgpu_optimize_sim3_batch_device(int batch, const orbgpu_sim3opt
                                                  const float* d_obs2, const float* d_inv_sigma2_1,
                                                  const float* d_inv_sigma2_2, orbgpu_sim3opt_result* d_results,
                                                  uint8_t* d_removed, void* stream) {
-    if (batch < 0 || total_corr < 0) return orbgpu::fail(ORBGPU_ERR_ARG, "negative batch or total_corr");
-    if (batch > 0 && (!d_jobs || !d_results)) return orbgpu::fail(ORBGPU_ERR_ARG, "null jobs or results");
-    if (batch > 0 && total_corr > 0 &&
-        (!d_P1c || !d_P2c || !d_obs1 || !d_obs2 || !d_inv_sigma2_1 || !d_inv_sigma2_2 || !d_removed))
-        return orbgpu::fail(ORBGPU_ERR_ARG, "null correspondence array");
+    if (int rc = orbgpu::check_batch_args(
+            batch, total_corr, "total_corr", d_jobs && d_results,
+            d_P1c && d_P2c && d_obs1 && d_obs2 && d_inv_sigma2_1 && d_inv_sigma2_2 && d_removed, "correspondence"))
+        return rc;
     if (batch == 0) return ORBGPU_OK;
     if (int rc = orbgpu::check_device()) return rc;
     (void)hipGetLastError();
@@ -586,22 +413,15 @@ extern "C" int orbgpu_optimize_sim3_batch(int batch, const orbgpu_sim3opt_job* j
                                           const float* inv_sigma2_1, const float* inv_sigma2_2,
                                           orbgpu_sim3opt_result* results, uint8_t* removed) {
     using namespace orbgpu;
-    if (batch < 0 || total_corr < 0) return fail(ORBGPU_ERR_ARG, "negative batch or total_corr");
-    if (batch > 0 && (!jobs || !results)) return fail(ORBGPU_ERR_ARG, "null jobs or results");
-    if (batch > 0 && total_corr > 0 && (!P1c || !P2c || !obs1 || !obs2 || !inv_sigma2_1 || !inv_sigma2_2 || !removed))
-        return fail(ORBGPU_ERR_ARG, "null correspondence array");
-    for (int b = 0; b < batch; ++b) {
-        const orbgpu_sim3opt_job& j = jobs[b];
-        if (j.n < 0 || j.offset < 0 || (long long)j.offset + j.n > (long long)total_corr)
-            return fail(ORBGPU_ERR_ARG, "job " + std::to_string(b) + " is out of the array bounds");
-    }
+    int rc = check_batch_args(batch, total_corr, "total_corr", jobs && results,
+                              P1c && P2c && obs1 && obs2 && inv_sigma2_1 && inv_sigma2_2 && removed, "correspondence");
+    if (rc || (rc = check_job_ranges(batch, jobs, total_corr))) return rc;
     if (batch == 0) return ORBGPU_OK;
     if (total_corr == 0) {  // every job has n == 0: nothing to optimise, nothing to launch
         for (int b = 0; b < batch; ++b) empty_result(jobs[b], results[b]);
         return ORBGPU_OK;
     }
-    int rc = check_device();
-    if (rc) return rc;
+    if ((rc = check_device())) return rc;
     const size_t tc = (size_t)total_corr;
     HostCtx* ctx;
     if ((rc = host_ctx(&ctx))) return rc;

@@ -9,11 +9,10 @@ SE3Quat (types/se3quat.h:58-64, 104-110, 217-257, 280-285).
 Sequential float64, the float casts where the reference has them: the stereo
 projection's invz, Huber's dsqr, the classification's (float)chi2 >
 (float)threshold, inputs and the returned pose in float32.  The quaternion
-algebra is Eigen 3's as recalled (Quaternion(Matrix3), operator*,
-_transformVector, toRotationMatrix, normalize); pow(theta, 3) is written
-theta*theta*theta and the dense LDLT is a plain Cholesky whose non-positive
-pivot is the failed solve, taken as a rejected zero step.  g2o needs Eigen to
-compile, so parity against a g2o build is unpinned.
+algebra, the dense solve and the Levenberg-Marquardt loop are tests/lm_ref.py's,
+shared with sim3opt_ref.py; pow(theta, 3) is written theta*theta*theta and a
+failed solve is taken as a rejected zero step.  g2o needs Eigen to compile, so
+parity against a g2o build is unpinned.
 
 Per-edge terms are numpy element-wise expressions (one IEEE operation per
 numpy call, no fused multiply-add); sums over edges are np.sum; everything
@@ -26,44 +25,17 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import lm_ref
+from lm_ref import _div, levenberg, quat_from_R, quat_mul, quat_rotate, quat_to_R  # noqa: F401 (re-exported)
+
 F32 = np.float32
 TH_MONO, TH_STEREO = F32(5.991), F32(7.815)
 DELTA_MONO, DELTA_STEREO = float(F32(math.sqrt(5.991))), float(F32(math.sqrt(7.815)))
 DSQR_MONO, DSQR_STEREO = float(F32(DELTA_MONO * DELTA_MONO)), float(F32(DELTA_STEREO * DELTA_STEREO))
-DBL_MAX = float(np.finfo(np.float64).max)
 UPPER = [(j, k) for j in range(6) for k in range(j, 6)]  # the 21 entries of H
 
 
 # ---------------------------------------------------------------- SE3Quat: q = (x, y, z, w), t
-
-def quat_from_R(R):
-    """Eigen: Quaterniond(Matrix3d)"""
-    t = (R[0][0] + R[1][1]) + R[2][2]
-    q = [0.0] * 4
-    if t > 0:
-        t = math.sqrt(t + 1.0)
-        q[3] = 0.5 * t
-        t = 0.5 / t
-        q[0] = (R[2][1] - R[1][2]) * t
-        q[1] = (R[0][2] - R[2][0]) * t
-        q[2] = (R[1][0] - R[0][1]) * t
-    else:
-        i = 0
-        if R[1][1] > R[0][0]:
-            i = 1
-        if R[2][2] > R[i][i]:
-            i = 2
-        j = (i + 1) % 3
-        k = (j + 1) % 3
-        s = ((R[i][i] - R[j][j]) - R[k][k]) + 1.0
-        t = math.sqrt(s) if s >= 0 else float("nan")
-        q[i] = 0.5 * t
-        t = 0.5 / t if t != 0 else float("inf")
-        q[3] = (R[k][j] - R[j][k]) * t
-        q[j] = (R[j][i] + R[i][j]) * t
-        q[k] = (R[k][i] + R[i][k]) * t
-    return q
-
 
 def quat_normalized(q):
     """SE3Quat::normalizeRotation"""
@@ -71,45 +43,6 @@ def quat_normalized(q):
         q = [-v for v in q]
     n = math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
     return [_div(v, n) for v in q]
-
-
-def _div(a, b):
-    try:
-        return a / b
-    except ZeroDivisionError:
-        return float("nan") if a == 0 or a != a else math.copysign(float("inf"), a) * math.copysign(1.0, b)
-
-
-def quat_mul(a, b):
-    ax, ay, az, aw = a
-    bx, by, bz, bw = b
-    return [((aw * bx + ax * bw) + ay * bz) - az * by,
-            ((aw * by + ay * bw) + az * bx) - ax * bz,
-            ((aw * bz + az * bw) + ax * by) - ay * bx,
-            ((aw * bw - ax * bx) - ay * by) - az * bz]
-
-
-def quat_rotate(q, v):
-    """Eigen's _transformVector on v = (x, y, z) scalars or arrays"""
-    qx, qy, qz, qw = q
-    ux = qy * v[2] - qz * v[1]
-    uy = qz * v[0] - qx * v[2]
-    uz = qx * v[1] - qy * v[0]
-    ux, uy, uz = ux + ux, uy + uy, uz + uz
-    return ((v[0] + qw * ux) + (qy * uz - qz * uy),
-            (v[1] + qw * uy) + (qz * ux - qx * uz),
-            (v[2] + qw * uz) + (qx * uy - qy * ux))
-
-
-def quat_to_R(q):
-    x, y, z, w = q
-    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
-    twx, twy, twz = tx * w, ty * w, tz * w
-    txx, txy, txz = tx * x, ty * x, tz * x
-    tyy, tyz, tzz = ty * y, tz * y, tz * z
-    return [[1.0 - (tyy + tzz), txy - twz, txz + twy],
-            [txy + twz, 1.0 - (txx + tzz), tyz - twx],
-            [txz - twy, tyz + twx, 1.0 - (txx + tyy)]]
 
 
 def se3_from_T(T):
@@ -210,13 +143,8 @@ def edge_jacobians(p, stereo, K, bf):
 
 
 def huber(chi2, stereo):
-    """RobustKernelHuber::robustify: (rho[0], rho[1])"""
-    delta = np.where(stereo, DELTA_STEREO, DELTA_MONO)
-    dsqr = np.where(stereo, DSQR_STEREO, DSQR_MONO)
-    with np.errstate(all="ignore"):
-        sq = np.sqrt(chi2)
-        inl = chi2 <= dsqr
-        return np.where(inl, chi2, (2.0 * sq) * delta - dsqr), np.where(inl, 1.0, delta / sq)
+    """RobustKernelHuber::robustify with the edge type's delta: (rho[0], rho[1])"""
+    return lm_ref.huber(chi2, np.where(stereo, DELTA_STEREO, DELTA_MONO), np.where(stereo, DSQR_STEREO, DSQR_MONO))
 
 
 def build_system(est, Xw, obs, w, K, bf, active, robust):
@@ -242,37 +170,6 @@ def build_system(est, Xw, obs, w, K, bf, active, robust):
             c = rho1 * ((J[:, 0, j] * we[:, 0] + J[:, 1, j] * we[:, 1]) + J[:, 2, j] * we[:, 2])
             b[j] = -float(np.sum(c))
         return H, b, float(np.sum(rho0))
-
-
-def solve6(H, b, lam):
-    """(H + lam I) x = b by Cholesky; None when a pivot is not positive"""
-    A = [[float(H[i][j]) + (lam if i == j else 0.0) for j in range(6)] for i in range(6)]
-    L = [[0.0] * 6 for _ in range(6)]
-    for j in range(6):
-        s = A[j][j]
-        for k in range(j):
-            s -= L[j][k] * L[j][k]
-        if not s > 0:
-            return None
-        L[j][j] = math.sqrt(s)
-        for i in range(j + 1, 6):
-            s = A[i][j]
-            for k in range(j):
-                s -= L[i][k] * L[j][k]
-            L[i][j] = s / L[j][j]
-    y = [0.0] * 6
-    for i in range(6):
-        s = float(b[i])
-        for k in range(i):
-            s -= L[i][k] * y[k]
-        y[i] = s / L[i][i]
-    x = [0.0] * 6
-    for i in range(5, -1, -1):
-        s = y[i]
-        for k in range(i + 1, 6):
-            s -= L[k][i] * x[k]
-        x[i] = s / L[i][i]
-    return x
 
 
 # ---------------------------------------------------------------- Optimizer::PoseOptimization
@@ -304,62 +201,11 @@ def pose_optimization(Tcw0, Xw, obs, inv_sigma2, K, bf):
     for it in range(4):
         robust = it < 3
         est = se3_from_T(Tcw0)
-        trial = est
         active = ~flagged
-        H, b, cur_chi = build_system(est, Xw, obs, w, K, bf, active, robust)
-        max_diag = 0.0
-        for j in range(6):  # std::max(fabs(h), maxDiagonal)
-            a = abs(float(H[j][j]))
-            max_diag = max_diag if a < max_diag else a
-        lam = 1e-5 * max_diag
-        ni = 2.0
-        stop_bad = 0
-        tr = SimpleNamespace(iterations=0, rejected=0, lam=[], trials=[], chi_after=[], chi2=None)
-        for _ in range(10):
-            tr.iterations += 1
-            tr.lam.append(lam)
-            ini_chi = cur_chi
-            rho = 0.0
-            qmax = 0
-            while True:
-                x = solve6(H, b, lam)
-                ok = x is not None
-                if not ok:
-                    x = [0.0] * 6
-                trial = se3_mul(se3_exp(x), est) if ok else est
-                Ht, bt, tmp_chi = build_system(trial, Xw, obs, w, K, bf, active, robust)
-                if not ok:
-                    tmp_chi = DBL_MAX
-                scale = 0.0
-                for j in range(6):
-                    scale += x[j] * (lam * x[j] + float(b[j]))
-                scale += 1e-3
-                rho = _div(cur_chi - tmp_chi, scale)
-                if rho > 0 and math.isfinite(tmp_chi):
-                    t3 = 2.0 * rho - 1.0
-                    alpha = min(1.0 - (t3 * t3) * t3, 2.0 / 3.0)
-                    lam *= max(1.0 / 3.0, alpha)
-                    ni = 2.0
-                    cur_chi = tmp_chi
-                    est, H, b = trial, Ht, bt
-                    tr.trials.append(True)
-                else:
-                    lam *= ni
-                    ni *= 2.0
-                    tr.rejected += 1
-                    tr.trials.append(False)
-                tr.chi_after.append(cur_chi)
-                qmax += 1
-                if not (rho < 0 and qmax < 10):
-                    break
-            if qmax == 10 or rho == 0:
-                break
-            if (ini_chi - cur_chi) * 1e3 < ini_chi:
-                stop_bad += 1
-            else:
-                stop_bad = 0
-            if stop_bad >= 3:
-                break
+        build = lambda e: build_system(e, Xw, obs, w, K, bf, active, robust)
+        # the kernel takes an accepted trial's system from the trial pass; building it again at the
+        # same estimate gives the same bits
+        est, trial, tr = levenberg(est, 6, 10, build, lambda t: build(t)[2], lambda e, x: se3_mul(se3_exp(x), e))
         # classification: active edges keep the error of the last trial, flagged ones are recomputed
         _, chi_trial, _ = edge_errors(trial, Xw, obs, w, K, bf)
         _, chi_est, _ = edge_errors(est, Xw, obs, w, K, bf)

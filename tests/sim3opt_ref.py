@@ -8,11 +8,10 @@ BaseBinaryEdge::linearizeOplus and the robust branch of constructQuadraticForm
 (core/optimization_algorithm_levenberg.cpp:61-189).
 
 Sequential float64; inputs, th2, Huber's delta and dsqr and the returned T12 in
-float32 where the reference has them.  The quaternion helpers are those of
-tests/poseopt_ref.py (Eigen 3's as recalled); the dense LDLT is a plain
-Cholesky whose non-positive pivot is the failed solve, taken as a rejected
-zero step.  g2o needs Eigen to compile, so parity against a g2o build is
-unpinned.
+float32 where the reference has them.  The quaternion helpers, the dense solve
+and the Levenberg-Marquardt loop are tests/lm_ref.py's, shared with
+poseopt_ref.py; a failed solve is taken as a rejected zero step.  g2o needs
+Eigen to compile, so parity against a g2o build is unpinned.
 
 Per-edge terms are numpy element-wise expressions (one IEEE operation per
 numpy call, no fused multiply-add); sums over edges are np.sum; everything
@@ -26,7 +25,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from poseopt_ref import DBL_MAX, _div, quat_from_R, quat_mul, quat_rotate, quat_to_R
+from lm_ref import _div, huber, levenberg, quat_from_R, quat_mul, quat_rotate, quat_to_R
 
 F32 = np.float32
 DELTA = 1e-9                  # base_binary_edge.hpp:147
@@ -189,14 +188,6 @@ def numeric_jacobians(S, p, fix_scale):
     return J12, J21
 
 
-def huber(chi2, delta, dsqr):
-    """RobustKernelHuber::robustify: (rho[0], rho[1])"""
-    with np.errstate(all="ignore"):
-        sq = np.sqrt(chi2)
-        inl = chi2 <= dsqr
-        return np.where(inl, chi2, (2.0 * sq) * delta - dsqr), np.where(inl, 1.0, delta / sq)
-
-
 def _interleaved_sum(a, b):
     """sum over the edges in the graph's order: e12, e21 of each correspondence in turn"""
     return float(np.sum(np.stack([a, b], 1).reshape(-1)))
@@ -229,99 +220,15 @@ def build_system(S, p, fix_scale, delta, dsqr):
         return H, b, _interleaved_sum(terms[0][0], terms[1][0])
 
 
-def solve7(H, b, lam):
-    """(H + lam I) x = b by Cholesky; None when a pivot is not positive"""
-    n = 7
-    A = [[float(H[i][j]) + (lam if i == j else 0.0) for j in range(n)] for i in range(n)]
-    L = [[0.0] * n for _ in range(n)]
-    for j in range(n):
-        s = A[j][j]
-        for k in range(j):
-            s -= L[j][k] * L[j][k]
-        if not s > 0:
-            return None
-        L[j][j] = math.sqrt(s)
-        for i in range(j + 1, n):
-            s = A[i][j]
-            for k in range(j):
-                s -= L[i][k] * L[j][k]
-            L[i][j] = s / L[j][j]
-    y = [0.0] * n
-    for i in range(n):
-        s = float(b[i])
-        for k in range(i):
-            s -= L[i][k] * y[k]
-        y[i] = s / L[i][i]
-    x = [0.0] * n
-    for i in range(n - 1, -1, -1):
-        s = y[i]
-        for k in range(i + 1, n):
-            s -= L[k][i] * x[k]
-        x[i] = s / L[i][i]
-    return x
-
-
 def optimize(est, p, iterations, fix_scale, delta, dsqr):
     """SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg
     on the one free vertex: (estimate, last trial, trace)"""
-    tr = SimpleNamespace(iterations=0, rejected=0, trials=[], chi_after=[])
-    trial = est
-    lam = ni = 0.0
-    stop_bad = 0
-    for it in range(iterations):
-        H, b, cur_chi = build_system(est, p, fix_scale, delta, dsqr)
-        if it == 0:
-            max_diag = 0.0
-            for j in range(7):  # std::max(fabs(h), maxDiagonal)
-                a = abs(float(H[j][j]))
-                max_diag = max_diag if a < max_diag else a
-            lam = 1e-5 * max_diag
-            ni = 2.0
-            stop_bad = 0
-        tr.iterations += 1
-        ini_chi = cur_chi
-        rho = 0.0
-        qmax = 0
-        while True:
-            x = solve7(H, b, lam)
-            ok = x is not None
-            if not ok:
-                x = [0.0] * 7
-            if fix_scale:
-                x[6] = 0.0  # oplusImpl zeroes the solver's own x[6] through its const_cast: computeScale sees it
-            trial = oplus(est, x, fix_scale) if ok else est
-            tmp_chi = robust_chi2(trial, p, delta, dsqr) if ok else DBL_MAX
-            scale = 0.0
-            for j in range(7):
-                scale += x[j] * (lam * x[j] + float(b[j]))
-            scale += 1e-3
-            rho = _div(cur_chi - tmp_chi, scale)
-            if rho > 0 and math.isfinite(tmp_chi):
-                t3 = 2.0 * rho - 1.0
-                alpha = min(1.0 - (t3 * t3) * t3, 2.0 / 3.0)
-                lam *= max(1.0 / 3.0, alpha)
-                ni = 2.0
-                cur_chi = tmp_chi
-                est = trial
-                tr.trials.append(True)
-            else:
-                lam *= ni
-                ni *= 2.0
-                tr.rejected += 1
-                tr.trials.append(False)
-            tr.chi_after.append(cur_chi)
-            qmax += 1
-            if not (rho < 0 and qmax < 10):
-                break
-        if qmax == 10 or rho == 0:
-            break
-        if (ini_chi - cur_chi) * 1e3 < ini_chi:
-            stop_bad += 1
-        else:
-            stop_bad = 0
-        if stop_bad >= 3:
-            break
-    return est, trial, tr
+    def step(S, x):
+        if fix_scale:
+            x[6] = 0.0  # oplusImpl zeroes the solver's own x[6] through its const_cast: computeScale sees it
+        return oplus(S, x, fix_scale)
+    return levenberg(est, 7, iterations, lambda S: build_system(S, p, fix_scale, delta, dsqr),
+                     lambda S: robust_chi2(S, p, delta, dsqr), step)
 
 
 # ---------------------------------------------------------------- Optimizer::OptimizeSim3
