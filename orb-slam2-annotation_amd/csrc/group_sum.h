@@ -1,6 +1,6 @@
 // group_sum.h -- sums over lane groups on DPP (full-rate VALU lane moves, no
 // LDS crossbar round trips): the reductions inside the one-sided Jacobi
-// sweeps of init_models.hip and epnp_wave.h, which are long dependent chains
+// sweeps of init_models.hip and epnp.h, which are long dependent chains
 // where ds_bpermute's latency set the pace.
 #pragma once
 

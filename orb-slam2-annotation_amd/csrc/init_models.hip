@@ -32,10 +32,10 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/orbgpu_init.h"
-#include "epnp.h"
 #include "group_sum.h"
 #include "jacobi_group.h"
 #include "jacobi_lds.h"
+#include "small_svd.h"
 #include "host_common.h"
 
 namespace {
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(kModelThreads) void init_models_kernel(const float*
         // singular triples
         double B[9], sv[3], V[9];
         for (int k = 0; k < 9; ++k) B[k] = nv[k];
-        orbgpu::epnp::svd_hestenes<3, 3>(B, sv, V);
+        orbgpu::svd_hestenes<3, 3>(B, sv, V);
         int jm = 0;
         for (int j = 1; j < 3; ++j)
             if (sv[j] < sv[jm]) jm = j;

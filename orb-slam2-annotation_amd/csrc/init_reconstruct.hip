@@ -29,7 +29,7 @@
 #include <vector>
 
 #include "../../include/orbgpu_init.h"
-#include "epnp.h"
+#include "small_svd.h"
 #include "host_common.h"
 #include "host_ctx.h"
 #include "group_sum.h"
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(kRecThreads) void check_rt_kernel(const float4* __r
                 A[12 + c] = (double)(p.w * H.P2[8 + c] - H.P2[4 + c]);
             }
             double s[4], v[16];
-            epnp::svd_hestenes<4, 4>(A, s, v);
+            svd_hestenes<4, 4>(A, s, v);
             int jmin = 0;
             for (int j = 1; j < 4; ++j)
                 if (s[j] < s[jmin]) jmin = j;
@@ -250,7 +250,7 @@ double det3(const float* m) {  // cv::determinant of a 3x3 CV_32F (double)
 void svd3(const float* M, float* w, float* U, float* Vt) {
     double a[9], s[3], v[9];
     for (int k = 0; k < 9; ++k) a[k] = M[k];
-    epnp::svd_hestenes<3, 3>(a, s, v);
+    svd_hestenes<3, 3>(a, s, v);
     int o[3] = {0, 1, 2};
     std::sort(o, o + 3, [&](int x, int y) { return s[x] > s[y]; });
     double u[3][3], vv[3][3];

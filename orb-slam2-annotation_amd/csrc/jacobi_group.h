@@ -5,7 +5,7 @@
 // column norms are the singular values and the columns of V the right
 // singular vectors (cv::SVDecomp's vt rows, cvSVD's V).  Used by
 // init_models.hip (the 9-column DLT matrices of ComputeH21 / ComputeF21) and
-// epnp_wave.h (the 12 x 12 M^T M of EPnP).
+// epnp.h (the 12 x 12 M^T M of a minimal set that takes the eigen path).
 //
 // Two choices make it fast on a wave:
 //   * round-robin (tournament) order: a sweep is M-1 rounds of M/2 DISJOINT
@@ -101,7 +101,7 @@ __device__ __forceinline__ bool jacobi_rotation_fast(double alpha, double beta, 
     return !skip;
 }
 
-// the rotation the sequential Jacobis (epnp.h) use: IEEE on the host, the
+// the rotation the sequential Jacobis (small_svd.h) use: IEEE on the host, the
 // fast reciprocals on the device (HIP host/device overloading)
 __host__ inline bool jacobi_rot(double alpha, double beta, double gamma, double negl, double& c, double& s) {
     return jacobi_rotation(alpha, beta, gamma, negl, c, s);

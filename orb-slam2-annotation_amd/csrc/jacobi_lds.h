@@ -6,8 +6,9 @@
 // column loads, an 8-lane DPP dot product, the rotation, the updates, two
 // stores) instead of the ~400 of jacobi_group.h's rows-on-lanes form, where
 // one lane carries a whole row of A and V and every pair of the round runs
-// through its instruction stream (EPnP's Refine: 3.1 k cycles per round on
-// one wave, 136 us per 12 x 12 decomposition).
+// through its instruction stream (EPnP's Refine on that form: 3.1 k cycles
+// per round on one wave, 136 us per 12 x 12 decomposition; epnp.h now runs
+// its 12 x 12 and its three 6 x 5 here).
 //
 // Same rotation (jacobi_rotation_fast), same tournament order
 // (jacobi_col), same convergence and null-column tests as hestenes_group;

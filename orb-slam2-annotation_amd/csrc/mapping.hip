@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "../../include/orbgpu_mapping.h"
-#include "epnp.h"
+#include "small_svd.h"
 #include "host_common.h"
 
 namespace orbgpu {
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kMapThreads) void triangulate_kernel(const orbgpu_m
             M[12 + c] = (double)(xn2[1] * B.Tcw[8 + c] - B.Tcw[4 + c]);
         }
         double s[4], v[16];
-        epnp::svd_hestenes<4, 4>(M, s, v);
+        svd_hestenes<4, 4>(M, s, v);
         int jmin = 0;
         for (int j = 1; j < 4; ++j)
             if (s[j] < s[jmin]) jmin = j;

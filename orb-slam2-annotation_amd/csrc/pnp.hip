@@ -1,7 +1,7 @@
 // pnp.hip -- PnPsolver's RANSAC loop (src/PnPsolver.cpp:203-349) for a batch
 // of solvers (one per relocalisation candidate keyframe), in two launches:
 //   1  pnp_hyp_kernel: 16 lanes per hypothesis (four per wave) run EPnP
-//      (epnp_wave.h) on its minimal set of 4 correspondences and score it
+//      (epnp.h) on its minimal set of 4 correspondences and score it
 //      (CheckInliers :352-386, the group's lanes over the correspondences)
 //      -- speculative, all n_hyp of every solver;
 //   2  pnp_score_kernel, one 256-thread block per solver, chunks of 256
@@ -19,7 +19,6 @@
 // methods and the null space of a minimal set is only defined up to a basis.
 #include "../../include/orbgpu_ransac.h"
 #include "epnp.h"
-#include "epnp_wave.h"
 #include "ransac_kernels.h"
 
 namespace orbgpu {

@@ -184,9 +184,7 @@ def _pose_close(Tg, R, t):
     assert np.abs(Tg[:3, 3] - t).max() <= 1e-3 * (1 + np.abs(t).max())
 
 
-@pytest.mark.gpu
-def test_pnp_gpu_batch_vs_oracle():
-    ransac = _ransac()
+def _oracle_cases():
     rng = np.random.default_rng(9)
     cases = []
     for b in range(16):
@@ -197,6 +195,13 @@ def test_pnp_gpu_batch_vs_oracle():
         samples = np.stack([rng.choice(n, 4, replace=False) for _ in range(n_hyp)]).astype(np.int32)
         min_inl = max(int(np.float32(n) * np.float32(0.5)), 10)
         cases.append((P, samples, min_inl))
+    return cases
+
+
+def _run_batch(cases):
+    """(P, samples, min_inliers) cases as one orbgpu_pnp_ransac_batch call: the problem records, the
+    result records and the best and refined masks"""
+    ransac = _ransac()
     arr = (ransac.PnPProblem * len(cases))()
     P3, P2, E, S = [], [], [], []
     off = soff = 0
@@ -211,6 +216,13 @@ def test_pnp_gpu_batch_vs_oracle():
     rm = np.zeros(off, np.uint8)
     res = ransac.pnp_ransac_batch(arr, np.concatenate(P3), np.concatenate(P2), np.concatenate(E),
                                   np.concatenate(S), bm, rm)
+    return arr, res, bm, rm
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_batch_vs_oracle():
+    cases = _oracle_cases()
+    arr, res, bm, rm = _run_batch(cases)
     nfound = 0
     for b, (P, samples, min_inl) in enumerate(cases):
         g = res[b]

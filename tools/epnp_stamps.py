@@ -3,7 +3,7 @@
 Run on the GPU box:
   ORBGPU_LIBRARY=orb-slam2-annotation_amd/liborbgpu_stamps.so python tools/epnp_stamps.py [n] [n_hyp]
 Prints the s_memtime deltas (shader clock cycles) between the phase marks of
-epnp_wave.h's compute_pose_group for one minimal-set hypothesis (G = 16) and
+csrc/epnp.h's compute_pose_group for one minimal-set hypothesis (G = 16) and
 for the first Refine (G = 64), and pnp_score_kernel's phases."""
 import ctypes
 import sys
@@ -37,15 +37,17 @@ L.orbgpu_debug_epnp_stamps.argtypes = [ctypes.c_void_p]
 st = np.zeros((3, 32), np.uint64)
 assert L.orbgpu_debug_epnp_stamps(st.ctypes.data) == 0
 st = st.astype(np.int64)
-names = ["start", "control pts", "pinv(CC)", "M^T M", "Jacobi 12x12", "canonical null", "L 6x10",
-         "svd_solve 6x4", "gauss-newton 1", "r_and_t 1", "svd_solve 6x3", "gauss-newton 2", "r_and_t 2",
-         "svd_solve 6x5", "gauss-newton 3", "r_and_t 3 / end"]
+# stamps 0-8 and 15 (the three beta approximations run side by side); 16 holds the 12 x 12 Jacobi's sweeps
+names = {1: "control pts", 2: "pinv(CC)", 3: "M^T M", 4: "Jacobi 12x12", 5: "canonical null", 6: "L 6x10",
+         7: "6x5 solve + betas", 8: "gauss-newton", 15: "R and t / end"}
 for row, title in ((0, "hypothesis (G=16, n=4)"), (1, "Refine (G=64)")):
     s = st[row]
     print(f"== {title}: total {s[15] - s[0]} cycles, Jacobi sweeps {s[16]}")
-    for k in range(1, 16):
-        if s[k] and s[k - 1]:
-            print(f"  {names[k]:18s} {s[k] - s[k - 1]:8d}")
+    prev = 0
+    for k, name in names.items():  # a minimal set that solves its null space on lanes skips 3 and 4
+        if s[k]:
+            print(f"  {name:18s} {s[k] - s[prev]:8d}")
+            prev = k
 s = st[2]
 print("== pnp_score_kernel (solver 0)")
 for k, nm in ((1, "to first best mask"), (2, "inlier list"), (3, "Refine"), (4, "to end")):
