@@ -124,14 +124,16 @@ typedef struct orbgpu_pnp_problem {
     float fu, fv, uc, vc;
 } orbgpu_pnp_problem;
 
+/* Every byte of a result record is written by the call.  A pose the call did
+ * not produce is 16 zeros: the zero matrix stands for the empty cv::Mat. */
 typedef struct orbgpu_pnp_result {
     int found;           /* Refine() succeeded: iterate() returns mRefinedTcw */
     int consumed;        /* hypotheses consumed (mnIterations advance)      */
     int best_inliers;    /* mnBestInliers after the call                    */
     int best_hyp;        /* hypothesis that last became the best, or -1     */
-    int refined_inliers; /* mnRefinedInliers when found                     */
-    float best_Tcw[16];  /* mBestTcw when best_hyp >= 0 (row-major 4x4)     */
-    float refined_Tcw[16]; /* mRefinedTcw when found                        */
+    int refined_inliers; /* mnRefinedInliers when found, else 0             */
+    float best_Tcw[16];  /* mBestTcw when best_hyp >= 0 (row-major 4x4), else zeros */
+    float refined_Tcw[16]; /* mRefinedTcw when found, else zeros            */
 } orbgpu_pnp_result;
 
 /* Device scratch for orbgpu_pnp_ransac_batch_device(). */

@@ -258,8 +258,15 @@ __global__ __launch_bounds__(kThreads) void pnp_score_kernel(const orbgpu_pnp_pr
         R.best_inliers = s_state[0];
         R.best_hyp = s_state[1];
         R.refined_inliers = s_state[2] ? s_state[5] : 0;
-        if (s_state[1] >= 0) pose_to_tcw(HP[s_state[1]], R.best_Tcw);
-        if (s_state[2]) pose_to_tcw(s_ref, R.refined_Tcw);
+        // a zero matrix stands for the empty cv::Mat: every byte of the record is written
+        if (s_state[1] >= 0)
+            pose_to_tcw(HP[s_state[1]], R.best_Tcw);
+        else
+            for (int k = 0; k < 16; ++k) R.best_Tcw[k] = 0.f;
+        if (s_state[2])
+            pose_to_tcw(s_ref, R.refined_Tcw);
+        else
+            for (int k = 0; k < 16; ++k) R.refined_Tcw[k] = 0.f;
     }
 }
 

@@ -6,13 +6,18 @@ tolerance"): the refined pose Tcw of the GPU and of the oracle agree to
 |dR|_max <= 1e-3 and |dt|_max <= 1e-3 * (1 + |t|_max); integer outcomes
 (found, iterations consumed, best inlier count) must be identical, and the
 inlier masks may differ in at most 1 % of the correspondences (points whose
-reprojection error sits on the 5.991 sigma^2 threshold)."""
+reprojection error sits on the 5.991 sigma^2 threshold).  The best
+hypothesis' pose and mask are held to the same tolerance, a mask's sum equals
+its count exactly, and a pose the call did not produce is all zeros
+(_check_record).  The problems come from tests/pnp_cases.py."""
 import ctypes
 import math
+from functools import lru_cache
 
 import numpy as np
 import pytest
 
+import pnp_cases
 import pnp_ref
 import synth
 
@@ -198,24 +203,73 @@ def _oracle_cases():
     return cases
 
 
-def _run_batch(cases):
-    """(P, samples, min_inliers) cases as one orbgpu_pnp_ransac_batch call: the problem records, the
-    result records and the best and refined masks"""
+def _run_batch(cases, refined_fill=0):
+    """(P, samples, min_inliers[, best_inliers, best_mask]) cases as one orbgpu_pnp_ransac_batch call
+    (the last two: the state carried into the call, 0 and an all-zero mask when left out): the
+    problem records, the result records and the best and refined masks.  The refined mask goes in
+    holding refined_fill in every byte."""
     ransac = _ransac()
     arr = (ransac.PnPProblem * len(cases))()
-    P3, P2, E, S = [], [], [], []
+    P3, P2, E, S, BM = [], [], [], [], []
     off = soff = 0
-    for b, (P, samples, min_inl) in enumerate(cases):
+    for b, case in enumerate(cases):
+        P, samples, min_inl = case[:3]
         p = arr[b]
         n = len(P["P3w"])
-        p.n, p.offset, p.min_inliers, p.best_inliers, p.n_hyp, p.sample_offset = n, off, min_inl, 0, len(samples), soff
+        best, mask = (case[3], case[4]) if len(case) > 3 else (0, np.zeros(n, np.uint8))
+        assert len(mask) == n
+        p.n, p.offset, p.min_inliers, p.best_inliers, p.n_hyp, p.sample_offset = n, off, min_inl, best, len(samples), soff
         p.fu, p.fv, p.uc, p.vc = P["cam"]
-        P3.append(P["P3w"]); P2.append(P["P2"]); E.append(P["sigma2"] * np.float32(5.991)); S.append(samples)
+        P3.append(P["P3w"]); P2.append(P["P2"]); E.append(P["sigma2"] * np.float32(5.991))
+        S.append(np.asarray(samples, np.int32).reshape(-1, 4)); BM.append(np.asarray(mask, np.uint8))
         off += n; soff += len(samples)
-    bm = np.zeros(off, np.uint8)
-    rm = np.zeros(off, np.uint8)
+    bm = np.concatenate(BM)
+    rm = np.full(off, refined_fill, np.uint8)
     res = ransac.pnp_ransac_batch(arr, np.concatenate(P3), np.concatenate(P2), np.concatenate(E),
                                   np.concatenate(S), bm, rm)
+    return arr, res, bm, rm
+
+
+ZERO_POSE = bytes(64)  # the empty cv::Mat of a pose the call did not produce
+
+
+def _slices(arr, b, *masks):
+    off, n = arr[b].offset, arr[b].n
+    return [m[off:off + n] for m in masks]
+
+
+def _check_record(g, o, case, bm, rm, label):
+    """every word of the result record g and both masks of one problem against the oracle's o at
+    the file's tolerance: integers equal, poses within _pose_close, masks within the cap; a mask's
+    sum equal to its count exactly (both come from the same pnp_inlier on the same double pose);
+    a pose the call did not produce all zeros, and the best mask then as it came in"""
+    n = len(case[0]["P3w"])
+    cap = max(1, n // 100)
+    assert (g.found, g.consumed, g.best_hyp, g.best_inliers) == pnp_cases.outcome(o), label
+    if g.best_hyp >= 0:
+        _pose_close(g.best_Tcw, o["best_R"], o["best_t"])
+        diff = int((bm.astype(bool) != o["best_mask"]).sum())
+        assert diff <= cap, f"{label}: {diff} best-mask differences"
+        assert int(bm.sum()) == g.best_inliers, label
+    else:
+        assert bytes(g.best_Tcw) == ZERO_POSE, label
+        incoming = np.asarray(case[4], np.uint8) if len(case) > 3 else np.zeros(n, np.uint8)
+        assert bm.tobytes() == incoming.tobytes(), label
+    if g.found:
+        _pose_close(g.refined_Tcw, o["refined_R"], o["refined_t"])
+        diff = int((rm.astype(bool) != o["refined_mask"]).sum())
+        assert diff <= cap, f"{label}: {diff} refined-mask differences"
+        assert abs(g.refined_inliers - int(o["refined_mask"].sum())) <= cap, label
+        assert int(rm.sum()) == g.refined_inliers, label
+    else:
+        assert bytes(g.refined_Tcw) == ZERO_POSE, label
+        assert g.refined_inliers == 0, label
+
+
+def _check_batch(cases, oracles, run=None):
+    arr, res, bm, rm = run or _run_batch(cases)
+    for b, (case, o) in enumerate(zip(cases, oracles)):
+        _check_record(res[b], o, case, *_slices(arr, b, bm, rm), f"case {b}")
     return arr, res, bm, rm
 
 
@@ -237,6 +291,7 @@ def test_pnp_gpu_batch_vs_oracle():
             diff = (rm[off_b:off_b + n].astype(bool) != o["refined_mask"]).sum()
             assert diff <= max(1, n // 100), f"case {b}: {diff} refined-mask differences"
             assert abs(g.refined_inliers - int(o["refined_mask"].sum())) <= max(1, n // 100)
+        _check_record(g, o, cases[b], *_slices(arr, b, bm, rm), f"case {b}")
     assert nfound >= 6
 
 
@@ -272,3 +327,205 @@ def test_pnp_solver_iterate_consumes_the_reference_stream():
     for _ in range(4 * o["consumed"]):
         LIBC.rand()
     assert [ransac.rand() for _ in range(5)] == [LIBC.rand() for _ in range(5)]
+
+
+# --------------------------------------------------------------------------
+# every output word and code path of orbgpu_pnp_ransac_batch (tests/pnp_cases.py)
+# --------------------------------------------------------------------------
+def test_pnp_cases_held_best_and_carried_state_in_the_oracle():
+    """what the GPU tests of the held best, the padded replay and the carried state lean on"""
+    for k in pnp_cases.HELD_K:
+        case = pnp_cases.held_best_case(k)
+        assert len(case[1]) == pnp_cases.HELD_OUTCOME[k][1]
+        assert pnp_cases.outcome(pnp_cases.oracle(case)) == pnp_cases.HELD_OUTCOME[k], k
+    whole = pnp_cases.padded_oracle()
+    assert pnp_cases.outcome(whole) == pnp_cases.PADDED_OUTCOME
+    o1, o2, o3 = pnp_cases.carried_oracles()
+    assert tuple(pnp_cases.outcome(o) for o in (o1, o2, o3)) == pnp_cases.CARRIED_OUTCOME
+    assert o1["best_mask"].tobytes() == o2["best_mask"].tobytes() == whole["best_mask"].tobytes()
+    assert o3["refined_inliers"] == 6 and o3["best_mask"].tobytes() == o1["best_mask"].tobytes()
+
+
+def test_pnp_cases_chunk_boundary_in_the_oracle():
+    for key in pnp_cases.CHUNK:
+        o = pnp_cases.chunk_oracle(*key)
+        assert pnp_cases.outcome(o)[:3] == pnp_cases.CHUNK_OUTCOME[key], key
+
+
+def test_pnp_cases_refine_sets_exact_in_the_oracle():
+    """Refine on m chosen noise-free points: the oracle finds the true pose (the bounds of
+    test_epnp_oracle_exact_on_noise_free_points; measured 1.5e-7 on R and 1.1e-6 on t at most)"""
+    for m in pnp_cases.REFINE_M:
+        case = pnp_cases.refine_set_case(m)
+        o = pnp_cases.oracle(case)
+        assert pnp_cases.outcome(o) == (1, 1, -1, 320) and o["refined_inliers"] == 320, m
+        np.testing.assert_allclose(o["refined_R"], case[0]["R"], atol=1e-5)
+        np.testing.assert_allclose(o["refined_t"], case[0]["t"], atol=1e-4)
+
+
+def test_pnp_cases_single_hypotheses_and_eigen_path_in_the_oracle():
+    _, _, counts = pnp_cases.single_hyp_sets()
+    assert int((counts >= 4).sum()) == 49
+    assert int(((counts == 3) | (counts == 4)).sum()) <= 2 and int((counts > 4).sum()) >= 32
+    for case in pnp_cases.eigen_path_cases():
+        X = case[1][0]
+        assert len(set(X.tolist())) == 4 and X.min() >= 6
+        assert pnp_cases.outcome(pnp_cases.oracle(case))[:3] == (1, 1, 0)
+    D = pnp_cases.eigen_path_cases()[0][1][1:]
+    P3 = pnp_cases.eigen_path_cases()[0][0]["P3w"]
+    assert all(len(np.unique(P3[d], axis=0)) < 4 for d in D)  # each holds a 3D point twice
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", pnp_cases.HELD_K)
+def test_pnp_gpu_best_held_without_refined_pose(k):
+    """RANSAC runs out holding hypothesis 0 as its best and Refine never succeeds: the record that
+    PnPsolver::iterate serves mBestTcw and mvbBestInliers from (PnPsolver.cpp:284-297); Refine's
+    EPnP ran on k = 4, 5, 6, 10 correspondences"""
+    case = pnp_cases.held_best_case(k)
+    _check_batch([case], [pnp_cases.oracle(case)])
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_best_held_across_the_chunk_boundary():
+    """300 hypotheses: the best of hypothesis 0 is held over both LDS chunks of the replay"""
+    _check_batch([pnp_cases.padded_case()], [pnp_cases.padded_oracle()])
+
+
+@lru_cache(maxsize=None)
+def _chunk_batch():
+    cases = [pnp_cases.chunk_case(*key) for key in pnp_cases.CHUNK]
+    return (cases,) + tuple(_run_batch(cases))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("i", range(len(pnp_cases.CHUNK)))
+def test_pnp_gpu_first_qualifying_hypothesis_around_the_chunk_boundary(i):
+    """the first hypothesis that qualifies is number 255 .. 299 of 300, on either side of the replay's
+    chunk of 256 (or none qualifies and Refine fails): one batch of five, a case per parameter"""
+    cases, arr, res, bm, rm = _chunk_batch()
+    o = pnp_cases.chunk_oracle(*pnp_cases.CHUNK[i])
+    assert pnp_cases.outcome(o)[:3] == pnp_cases.CHUNK_OUTCOME[pnp_cases.CHUNK[i]]
+    _check_record(res[i], o, cases[i], *_slices(arr, i, bm, rm), f"case {pnp_cases.CHUNK[i]}")
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_chunk_boundary_problem_alone():
+    case = pnp_cases.chunk_case(42, 256)
+    _check_batch([case], [pnp_cases.chunk_oracle(42, 256)])
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_carried_state():
+    """the in/out contract of best_inliers and best_mask, as a second iterate() on one solver uses
+    it: call 2 gets call 1's count and its downloaded mask; with min_inliers = 5 its first
+    hypothesis runs Refine on the carried mask"""
+    o1, o2, o3 = pnp_cases.carried_oracles()
+    c1 = pnp_cases.carried_cases(0, None)[0]
+    arr, res, bm, rm = _check_batch([c1, pnp_cases.padded_case()], [o1, pnp_cases.padded_oracle()])
+    bm1, bm_whole = _slices(arr, 0, bm)[0].copy(), _slices(arr, 1, bm)[0]
+    _, c2, c3 = pnp_cases.carried_cases(res[0].best_inliers, bm1)
+    arr, res, bm, rm = _check_batch([c2, c3], [o2, o3])
+    for b in range(2):  # the carried mask is left as it came in, and is the single 300-hypothesis run's
+        assert _slices(arr, b, bm)[0].tobytes() == bm1.tobytes() == bm_whole.tobytes()
+    assert res[1].refined_inliers == 6
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_no_work_members_of_a_batch():
+    """n_hyp = 0 with carried state, and n = 0, beside a working problem: nothing consumed, the count
+    passed through, both masks as they came in, zero poses"""
+    P, samples, min_inl = pnp_cases.held_best_case(6)
+    carried = np.zeros(30, np.uint8)
+    carried[[0, 2, 3, 7, 11, 29]] = 1
+    none = np.zeros((0, 4), np.int32)
+    empty = {"P3w": np.zeros((0, 3), np.float32), "P2": np.zeros((0, 2), np.float32),
+             "sigma2": np.zeros(0, np.float32), "cam": P["cam"]}
+    cases = [(P, none, min_inl, 6, carried), (P, samples, min_inl), (empty, none, 4, 3, np.zeros(0, np.uint8)),
+             (P, none, min_inl, 6, carried)]
+    oracles = [pnp_cases.oracle(c) for c in cases]
+    arr, res, bm, rm = _check_batch(cases, oracles, run=_run_batch(cases, refined_fill=7))
+    for b in (0, 2, 3):
+        g = res[b]
+        assert (g.found, g.consumed, g.best_hyp, g.best_inliers, g.refined_inliers) == (0, 0, -1, cases[b][3], 0)
+        assert bytes(g.best_Tcw) == bytes(g.refined_Tcw) == ZERO_POSE
+        m_best, m_ref = _slices(arr, b, bm, rm)
+        assert m_best.tobytes() == cases[b][4].tobytes() and (m_ref == 7).all()
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_refine_on_chosen_sets_vs_truth():
+    """Refine's wave-wide EPnP on exactly m = 4 .. 320 chosen noise-free points (k = 4, 2, 0 null
+    vectors to canonicalise; m on either side of its lane strides 16 and 64 and of 256), one batch
+    of 18: against the oracle at the file tolerance, and against the true pose -- independent of
+    both restatements -- at the bounds the oracle itself meets"""
+    cases = [pnp_cases.refine_set_case(m) for m in pnp_cases.REFINE_M]
+    oracles = [pnp_cases.oracle(c) for c in cases]
+    arr, res, bm, rm = _check_batch(cases, oracles)
+    worst_R = worst_t = 0.0
+    for m, case, g in zip(pnp_cases.REFINE_M, cases, res):
+        assert (g.found, g.consumed, g.best_hyp, g.best_inliers, g.refined_inliers) == (1, 1, -1, 320, 320), m
+        T = np.array(g.refined_Tcw, np.float64).reshape(4, 4)
+        dR, dt = np.abs(T[:3, :3] - case[0]["R"]).max(), np.abs(T[:3, 3] - case[0]["t"]).max()
+        print(f"m = {m}: |dR| = {dR:.3g}, |dt| = {dt:.3g} against the truth")
+        worst_R, worst_t = max(worst_R, dR), max(worst_t, dt)
+        np.testing.assert_allclose(T[:3, :3], case[0]["R"], rtol=0, atol=1e-5, err_msg=f"m = {m}")
+        np.testing.assert_allclose(T[:3, 3], case[0]["t"], rtol=0, atol=1e-4, err_msg=f"m = {m}")
+    print(f"worst against the truth: |dR| = {worst_R:.3g}, |dt| = {worst_t:.3g}")
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_every_minimal_set_one_per_problem():
+    """64 minimal sets, each the only hypothesis of a problem of its own with min_inliers = 4, so
+    every set's pose, count and mask surface as the best (in a RANSAC run half the hypotheses score 0
+    and are never seen).  Sets whose oracle count is 3 or 4 sit on the threshold and are dropped."""
+    P, sets, counts = pnp_cases.single_hyp_sets()
+    cases = [(P, s[None], 4) for s in sets]
+    arr, res, bm, rm = _run_batch(cases)
+    pw, us = P["P3w"].astype(np.float64), P["P2"].astype(np.float64)
+    cam = tuple(float(c) for c in P["cam"])
+    cap = max(1, 60 // 100)
+    kept = 0
+    for b, (s, c) in enumerate(zip(sets, counts)):
+        if c in (3, 4):
+            continue
+        g = res[b]
+        if c < 4:
+            assert g.best_hyp == -1 and g.best_inliers == 0 and bytes(g.best_Tcw) == ZERO_POSE, b
+            continue
+        kept += 1
+        R, t, _ = pnp_ref.compute_pose(pw[s], us[s], cam)
+        mask = pnp_ref.check_inliers(R, t, P["P3w"], P["P2"], pnp_cases.maxerr(P), cam)
+        m_best = _slices(arr, b, bm)[0]
+        assert g.best_hyp == 0 and abs(g.best_inliers - c) <= cap, (b, g.best_inliers, c)
+        assert int((m_best.astype(bool) != mask).sum()) <= cap and int(m_best.sum()) == g.best_inliers, b
+        _pose_close(g.best_Tcw, R, t)
+    assert kept >= 32 and int(np.isin(counts, (3, 4)).sum()) <= 2
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_regular_set_on_the_eigen_path():
+    """a regular minimal set whose wave neighbours are degenerate takes null_space_from_mtm<16>
+    instead of the 12 x 12 solve: same best pose and mask as beside regular neighbours, and as the
+    oracle's.  Nothing is asserted on the degenerate sets themselves."""
+    cases = list(pnp_cases.eigen_path_cases())
+    oracles = [pnp_cases.oracle(c) for c in cases]
+    arr, res, bm, rm = _check_batch(cases, oracles)
+    assert all((g.found, g.consumed, g.best_hyp) == (1, 1, 0) for g in res)
+    Ta, Tb = (np.array(g.best_Tcw, np.float64).reshape(4, 4) for g in res)
+    _pose_close(Ta, Tb[:3, :3], Tb[:3, 3])
+    (ma,), (mb,) = _slices(arr, 0, bm), _slices(arr, 1, bm)
+    assert int((ma != mb).sum()) <= max(1, 60 // 100)
+
+
+@pytest.mark.gpu
+def test_pnp_gpu_batch_equals_alone():
+    """every byte of each result record and of both masks is the same from a batch as from the
+    problem run alone (all bytes of the record are defined)"""
+    for cases, run in ((pnp_cases.six_cases(), None), (_chunk_batch()[0], _chunk_batch()[1:])):
+        arr, res, bm, rm = run or _run_batch(cases)
+        for b, case in enumerate(cases):
+            arr1, res1, bm1, rm1 = _run_batch([case])
+            assert bytes(res[b]) == bytes(res1[0]), b
+            m_best, m_ref = _slices(arr, b, bm, rm)
+            assert m_best.tobytes() == bm1.tobytes() and m_ref.tobytes() == rm1.tobytes(), b
