@@ -13,18 +13,22 @@
  *   Sim3Solver::SetRansacParameters     src/Sim3Solver.cpp:111-141
  *   Sim3Solver::iterate                 src/Sim3Solver.cpp:147-221
  *
- * Scope of the round-robin call.  After a candidate's iterate() returns a
- * Sim3 the reference runs SearchBySim3 + OptimizeSim3 (:358-392, outside the
- * hot path) and stops at the first candidate whose optimisation keeps >= 20
- * inliers.  Here that verification is taken to pass, so a query ends at the
- * first RANSAC success in the reference's candidate order -- the result the
- * caller then verifies.  The verification's optimisation is now on the device
- * too: orbgpu_optimize_sim3_batch (orbgpu_sim3opt.h) is OptimizeSim3, so the
- * caller can run :358-398 on the returned Sim3 without g2o; it is a separate
- * call, not part of this one.  Everything up to that point is the reference's:
- * the same candidates discarded, the same hypotheses drawn from the same
- * glibc rand() stream in the same order (iterate(5) per candidate per round),
- * the same acceptance.
+ * Scope of the round-robin calls.  After a candidate's iterate() returns a
+ * Sim3 the reference runs SearchBySim3 + OptimizeSim3 on it (:358-392) and
+ * stops only at a candidate whose optimisation keeps >= 20 inliers; after a
+ * failed verification the for loop goes on with the next candidate of the
+ * same round, and the solver that returned stays alive with its state.
+ *   orbgpu_compute_sim3_batch_device takes the verification to pass: a query
+ *     ends at the first RANSAC success in the reference's candidate order.
+ *   orbgpu_compute_sim3_verified_batch_device is the whole
+ *     `while (nCandidates > 0 && !bMatch)` loop, verification included, on
+ *     the device: a resumable RANSAC kernel that keeps every solver's state,
+ *     SearchBySim3 through the projection matcher's SIM3_DIR variant both
+ *     ways with the agreement check, the gathers and the two optimisations of
+ *     OptimizeSim3, the 20-inlier decision and mg2oScw (:402-405).
+ * Everything up to a return is the reference's in both: the same candidates
+ * discarded, the same hypotheses drawn from the same glibc rand() stream in
+ * the same order (iterate(5) per candidate per round), the same acceptance.
  *
  * Random stream.  DUtils::Random is process-global, so the draws of a query
  * start where the caller's stream stands: each query carries the
@@ -43,7 +47,9 @@
 #include <stdint.h>
 
 #include "orbgpu.h"
+#include "orbgpu_proj.h"
 #include "orbgpu_ransac.h"
+#include "orbgpu_sim3opt.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -147,6 +153,93 @@ int orbgpu_compute_sim3_batch_device(int n_queries, const orbgpu_compute_sim3_qu
 /* Device pointer to candidate c's KF1 slots (mvnIndices1) inside the
  * workspace: int[match_stride], the first d_n_corr[c] valid. */
 const int* orbgpu_sim3_corr_kf1_slots(const void* d_workspace, int n_cand, int match_stride, int c);
+
+/* ---------------------------------------------------------------------- */
+/* The verified loop: `while (nCandidates > 0 && !bMatch)` with            */
+/* SearchBySim3 + OptimizeSim3 after every return (LoopClosing.cpp:339-411) */
+/* ---------------------------------------------------------------------- */
+
+/* What SearchBySim3 and OptimizeSim3's gathers read of a keyframe beyond its
+ * orbgpu_loop_keyframe entry; entry k of this table belongs to keyframe k of
+ * that one.  All pointers are device pointers; positions and validity of the
+ * MapPoints come from the orbgpu_loop_keyframe table (slot i = keypoint i =
+ * its MapPoint, GetIndexInKeyFrame = the slot). */
+typedef struct orbgpu_loop_keyframe_search {
+    orbgpu_proj_target target;      /* n, mvKeysUn, descriptors (16-byte aligned), bounds, scale pyramid,
+                                       Tcw = the keyframe's pose [Rcw tcw; 0 1] (the same numbers as the
+                                       orbgpu_loop_keyframe entry); u_right / occupied unused */
+    const uint8_t* mp_desc;         /* MapPoint::GetDescriptor() per slot, n x 32, 16-byte aligned */
+    const float* mp_min_dist;       /* mfMinDistance per slot */
+    const float* mp_max_dist;       /* mfMaxDistance per slot */
+    float inv_level_sigma2[16];     /* mvInvLevelSigma2 */
+} orbgpu_loop_keyframe_search;
+
+enum {
+    ORBGPU_SIM3_PENDING = 0,        /* more passes needed */
+    ORBGPU_SIM3_MATCHED = 1,        /* a candidate's OptimizeSim3 kept >= min_opt_inliers */
+    ORBGPU_SIM3_NO_MATCH = 2,       /* no candidate is live any more */
+    ORBGPU_SIM3_CAPACITY = 3        /* a keyframe exceeds the projection matcher's capacity (nothing truncated) */
+};
+
+typedef struct orbgpu_compute_sim3_verified_result {
+    int status;               /* ORBGPU_SIM3_*                                    */
+    int matched;              /* the candidate (0..n_cand-1) that passed, or -1   */
+    int round;                /* round of iterate() calls of the last return (-1: none) */
+    int verifications;        /* SearchBySim3 + OptimizeSim3 runs                 */
+    int hypotheses;           /* RANSAC iterations run by all candidates          */
+    int draws;                /* rand() values consumed (3 per iteration)         */
+    /* the last verification (zero / -1 when there was none) */
+    int last_cand;            /* its candidate, or -1                             */
+    int n_inliers;            /* nInliers of the iterate() call that returned     */
+    int n_found;              /* SearchBySim3's return value                      */
+    int n_gathered;           /* correspondences OptimizeSim3 gathered            */
+    float R12[9];             /* the RANSAC GetEstimatedRotation()                */
+    float t12[3];             /* GetEstimatedTranslation()                        */
+    float s12;                /* GetEstimatedScale()                              */
+    float T12[16];            /* the returned Scm, row-major [sR t; 0 1]          */
+    int pad;
+    orbgpu_sim3opt_result opt;   /* OptimizeSim3's whole result                   */
+    /* mg2oScw = gScm * Sim3(Rcw2, tcw2, 1.0) when matched, else zeros */
+    double Scw_q[4], Scw_t[3], Scw_s;
+    float Scw[16];            /* Converter::toCvMat(mg2oScw)                      */
+    orbgpu_rand_state rng_after; /* stream state after exactly the consumed draws */
+} orbgpu_compute_sim3_verified_result;
+
+/* Bytes of the opaque device state block of the verified call: per-candidate
+ * solver state (ORBGPU_LOOP_MAX_CANDIDATES per query), the per-query cursor
+ * and stream, the two projection calls with their point flags and match rows,
+ * the gathered correspondences, the sim3opt job / result and removed flags. */
+size_t orbgpu_compute_sim3_verified_workspace_bytes(int n_queries, int match_stride);
+
+/* The reference's loop for every query.  One *pass* advances every unfinished
+ * query to its next RANSAC return (or its end) and verifies that Sim3; n_passes
+ * >= 1 passes are enqueued on `stream` with no host synchronisation, and a
+ * pass does nothing for a finished query.  resume = 0 starts every query from
+ * its rng; resume = 1 continues from d_state as an earlier call with the same
+ * arguments left it.  A query's result, candidate states and rows do not
+ * depend on how the passes are split over calls or on the batch it runs in.
+ * A query still ORBGPU_SIM3_PENDING after the call needs more passes.
+ *   d_kf_search      table parallel to d_kfs
+ *   d_match12        SearchByBoW's rows as for orbgpu_sim3_setup_batch_device;
+ *                    d_workspace / d_n_corr as that call filled them
+ *   th_search        SearchBySim3's th (7.5f); th2: OptimizeSim3's (10.f);
+ *                    min_opt_inliers: 20
+ *   d_cand_states    per candidate, the solver state after the last pass
+ *                    (discarded: no longer scheduled)
+ *   d_rows           int[n_queries][3][match_stride], of the last verification,
+ *                    by KF1 slot: vbInliers (0/1); SearchBySim3's own agreed
+ *                    row (KF2 slot or -1); the final vpMapPointMatches after
+ *                    OptimizeSim3's removals (KF2 slot or -1) -- when matched,
+ *                    mvpCurrentMatchedPoints
+ * ORBGPU_ERR_ARG comes before the device is looked at. */
+int orbgpu_compute_sim3_verified_batch_device(
+    int n_queries, const orbgpu_compute_sim3_query* d_queries, int n_cand, const orbgpu_sim3_candidate* d_cands,
+    const orbgpu_loop_keyframe* d_kfs, const orbgpu_loop_keyframe_search* d_kf_search, const int* d_match12,
+    int match_stride, const void* d_workspace, const int* d_n_corr, orbgpu_sim3_ransac_params params, float th_search,
+    float th2, int min_opt_inliers, int n_passes, int resume, void* d_state,
+    orbgpu_compute_sim3_verified_result* d_results, orbgpu_sim3_candidate_state* d_cand_states, int* d_rows,
+    void* stream);
+
 
 #ifdef __cplusplus
 }

@@ -21,58 +21,15 @@
 #include "../../include/orbgpu_loop.h"
 #include "host_common.h"
 #include "orbgpu_internal.h"
-#include "sim3_device.h"
+#include "loop_device.h"
 
 namespace orbgpu {
 
 namespace {
 
-using namespace sim3dev;
+using namespace loopdev;  // the workspace layout and the RANSAC pieces shared with loop_verify.hip
 
 constexpr int kThreads = 256;       // sim3_setup_kernel
-#ifndef ORBGPU_SIM3_THREADS
-#define ORBGPU_SIM3_THREADS 512
-#endif
-constexpr int kQThreads = ORBGPU_SIM3_THREADS;  // compute_sim3_kernel: 8 scoring waves, 2 per SIMD
-constexpr int kWin = 256;  // hypotheses solved and scored per window
-constexpr int kMaxC = ORBGPU_LOOP_MAX_CANDIDATES;
-
-struct Workspace {  // SoA, candidate c at c * stride
-    float* X1;      // 3 per correspondence
-    float* X2;
-    float* e1;
-    float* e2;
-    int* idx1;
-    float2* P1;     // mvP1im1 / mvP2im2: FromCameraToImage of X1 / X2 (the ctor's, Sim3Solver.cpp:97-98)
-    float2* P2;
-};
-
-__host__ __device__ inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-__host__ __device__ inline Workspace carve(void* base, int n_cand, int stride) {
-    const size_t n = (size_t)n_cand * stride;
-    char* p = static_cast<char*>(base);
-    Workspace w;
-    w.X1 = reinterpret_cast<float*>(p);
-    p += align256(n * 12);
-    w.X2 = reinterpret_cast<float*>(p);
-    p += align256(n * 12);
-    w.e1 = reinterpret_cast<float*>(p);
-    p += align256(n * 4);
-    w.e2 = reinterpret_cast<float*>(p);
-    p += align256(n * 4);
-    w.idx1 = reinterpret_cast<int*>(p);
-    p += align256(n * 4);
-    w.P1 = reinterpret_cast<float2*>(p);
-    p += align256(n * 8);
-    w.P2 = reinterpret_cast<float2*>(p);
-    return w;
-}
-
-size_t workspace_bytes(int n_cand, int stride) {
-    const size_t n = (size_t)(n_cand > 0 ? n_cand : 1) * (stride > 0 ? stride : 1);
-    return 2 * align256(n * 12) + 3 * align256(n * 4) + 2 * align256(n * 8);
-}
 
 // mvnMaxError = 9.210*sigma^2 kept in a vector<size_t> (Sim3Solver.cpp:92-93)
 __device__ inline float max_error(float sigma2) { return (float)(unsigned long long)(9.210 * (double)sigma2); }
@@ -132,25 +89,6 @@ __global__ __launch_bounds__(kThreads) void sim3_setup_kernel(const orbgpu_sim3_
     if (tid == 0) n_corr[c] = base;
 }
 
-// glibc random_r TYPE_3 step (csrc/ransac.cpp restates the same generator):
-// returns the raw sum written into the state; rand() is raw >> 1
-__device__ inline uint32_t rand_next_raw(int32_t* r, int& f, int& b) {
-    const uint32_t val = (uint32_t)r[f] + (uint32_t)r[b];
-    r[f] = (int32_t)val;
-    if (++f >= 31) {
-        f = 0;
-        ++b;
-    } else if (++b >= 31) {
-        b = 0;
-    }
-    return val;
-}
-
-// DUtils::Random::RandomInt(0, d-1)
-__device__ inline int random_below(int32_t v, int d) {
-    return (int)(((double)v / ((double)2147483647 + 1.0)) * d);
-}
-
 __global__ __launch_bounds__(kQThreads) void compute_sim3_kernel(
     const orbgpu_compute_sim3_query* __restrict__ queries, const orbgpu_sim3_candidate* __restrict__ cands,
     const orbgpu_loop_keyframe* __restrict__ kfs, int stride, Workspace ws, const int* __restrict__ n_corr,
@@ -181,19 +119,7 @@ __global__ __launch_bounds__(kQThreads) void compute_sim3_kernel(
         }
         const int N = n_corr[c0 + tid];
         c_n[tid] = N;
-        int max_its = 0;
-        if (N >= 0) {
-            const float eps = (float)prm.min_inliers / (float)N;
-            int n_it;
-            if (prm.min_inliers == N) {
-                n_it = 1;
-            } else {
-                const double v = ceil(log(1.0 - prm.probability) / log(1.0 - pow((double)eps, 3.0)));
-                // an out-of-range double -> int conversion is INT_MIN on x86 (cvttsd2si)
-                n_it = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (int)0x80000000;
-            }
-            max_its = max(1, min(n_it, prm.max_iterations));
-        }
+        const int max_its = ransac_max_iterations(N, prm);
         c_max[tid] = max_its;
         c_its[tid] = 0;
         c_best[tid] = 0;
@@ -242,32 +168,7 @@ __global__ __launch_bounds__(kQThreads) void compute_sim3_kernel(
                 const int k = min(ipc, c_max[c] - c_sched[c]);  // iterations of this iterate() call
                 for (; cur_j < k && n < win; ++cur_j, ++n) {
                     // vAvailableIndices = mvAllIndices; 3 x RandomInt + swap-remove (Sim3Solver.cpp:172-183)
-                    const int N = c_n[c];
-                    int pos[2], val[2], nmod = 0;
-                    for (int d = 0; d < 3; ++d) {
-                        const int size = N - d;
-                        const uint32_t raw = rand_next_raw(s_r, rf, rb);
-                        s_gen[3 * n + d] = (int32_t)raw;
-                        const int r = random_below((int32_t)(raw >> 1), size);
-                        int idx = r;  // vAvailableIndices[r] after the earlier swaps
-                        for (int m = nmod - 1; m >= 0; --m)
-                            if (pos[m] == r) {
-                                idx = val[m];
-                                break;
-                            }
-                        int back = size - 1;  // vAvailableIndices.back()
-                        for (int m = nmod - 1; m >= 0; --m)
-                            if (pos[m] == size - 1) {
-                                back = val[m];
-                                break;
-                            }
-                        s_trip[n][d] = idx;
-                        if (d < 2) {
-                            pos[nmod] = r;
-                            val[nmod] = back;
-                            ++nmod;
-                        }
-                    }
+                    draw_triplet(c_n[c], s_r, rf, rb, &s_gen[3 * n], s_trip[n]);
                     s_slot_c[n] = c;
                     s_slot_r[n] = cur_round;
                 }
@@ -307,30 +208,9 @@ __global__ __launch_bounds__(kQThreads) void compute_sim3_kernel(
             const bool both = h1 < ns && s_slot_c[h1] == c;  // wave-uniform
             auto check = [&](int h, int hb, bool two) {  // hypotheses h (and hb when two) of candidate s_slot_c[h]
                 const int cc = s_slot_c[h];
-                const float* K1 = s_K[cc];
-                const float* K2 = s_K[cc] + 4;
-                const size_t o = (size_t)(c0 + cc) * stride;
-                const int N = c_n[cc];
-                int cnt = 0, cntb = 0;
-                for (int i0 = lane; i0 < N; i0 += 256) {
-                    bool in[4], inb[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int i = min(i0 + 64 * u, N - 1);
-                        const float* X1 = ws.X1 + 3 * (o + i);
-                        const float* X2 = ws.X2 + 3 * (o + i);
-                        const float2 p1 = ws.P1[o + i], p2 = ws.P2[o + i];
-                        const float e1 = ws.e1[o + i], e2 = ws.e2[o + i];
-                        in[u] = is_inlier_pre(s_hyp[h], K1, K2, X1, X2, p1, p2, e1, e2);
-                        inb[u] = two && is_inlier_pre(s_hyp[hb], K1, K2, X1, X2, p1, p2, e1, e2);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const bool live = i0 + 64 * u < N;
-                        cnt += __popcll(__ballot(in[u] && live));
-                        if (two) cntb += __popcll(__ballot(inb[u] && live));
-                    }
-                }
+                int cnt, cntb;
+                score_pair(ws, (size_t)(c0 + cc) * stride, c_n[cc], s_K[cc], s_K[cc] + 4, s_hyp[h], s_hyp[hb], two, lane,
+                           cnt, cntb);
                 if (lane == 0) {
                     s_cnt[h] = cnt;
                     if (two) s_cnt[hb] = cntb;

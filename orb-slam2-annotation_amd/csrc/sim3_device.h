@@ -1,6 +1,7 @@
 // sim3_device.h -- Sim3Solver device arithmetic shared by the RANSAC
-// kernels (sim3.hip: one iterate() call per solver; loop.hip: LoopClosing's
-// round-robin ComputeSim3 over all candidates of a query).
+// kernels (sim3.hip: one iterate() call per solver; loop.hip and
+// loop_verify.hip: LoopClosing's round-robin ComputeSim3 over all candidates
+// of a query).
 //   compute_sim3  ComputeSim3 (src/Sim3Solver.cpp:225-327): Horn's closed form
 //   is_inlier     CheckInliers' per-correspondence test (:331-358, Project
 //                 :378-400, FromCameraToImage :402-420)

@@ -12,6 +12,11 @@ include/orbgpu_loop.h (csrc/loop.hip) and include/orbgpu_bow.h.
   verification that follows is outside the hot path and taken to pass; its
   optimisation, OptimizeSim3, is a separate call: sim3opt.optimize_sim3_batch).
 
+``LoopBurst(..., search=KeyframeSearch(...))`` adds ``step_verified``: the
+reference's whole loop, with SearchBySim3 + OptimizeSim3 after every RANSAC
+return on the device and the search going on after a failed verification
+(orbgpu_compute_sim3_verified_batch_device, csrc/loop_verify.hip).
+
 Everything runs on the GPU in four launches per step (SearchByBoW batch,
 Sim3Solver set-up, ComputeSim3); there is no host fallback.
 """
@@ -23,7 +28,9 @@ import numpy as np
 
 import bow
 import orbgpu
+import proj
 import ransac
+import sim3opt
 
 _BOUND = False
 
@@ -59,6 +66,22 @@ class Sim3CandidateState(ctypes.Structure):
                 ("best_inliers", ctypes.c_int), ("discarded", ctypes.c_int), ("pad", ctypes.c_int)]
 
 
+class LoopKeyframeSearch(ctypes.Structure):
+    _fields_ = [("target", proj.Target), ("mp_desc", ctypes.c_void_p), ("mp_min_dist", ctypes.c_void_p),
+                ("mp_max_dist", ctypes.c_void_p), ("inv_level_sigma2", ctypes.c_float * 16)]
+
+
+class ComputeSim3VerifiedResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int), ("matched", ctypes.c_int), ("round", ctypes.c_int),
+                ("verifications", ctypes.c_int), ("hypotheses", ctypes.c_int), ("draws", ctypes.c_int),
+                ("last_cand", ctypes.c_int), ("n_inliers", ctypes.c_int), ("n_found", ctypes.c_int),
+                ("n_gathered", ctypes.c_int), ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3),
+                ("s12", ctypes.c_float), ("T12", ctypes.c_float * 16), ("pad", ctypes.c_int),
+                ("opt", sim3opt.Sim3OptResult), ("Scw_q", ctypes.c_double * 4), ("Scw_t", ctypes.c_double * 3),
+                ("Scw_s", ctypes.c_double), ("Scw", ctypes.c_float * 16), ("rng_after", ransac.RandState)]
+
+
+PENDING, MATCHED, NO_MATCH, CAPACITY = 0, 1, 2, 3
 MAX_CANDIDATES = 64
 
 
@@ -73,6 +96,11 @@ def _lib():
         L.orbgpu_compute_sim3_batch_device.argtypes = [i, vp, i, vp, vp, i, vp, vp, Sim3RansacParams, vp, vp, vp, vp]
         L.orbgpu_sim3_corr_kf1_slots.argtypes = [vp, i, i, i]
         L.orbgpu_sim3_corr_kf1_slots.restype = ctypes.c_void_p
+        L.orbgpu_compute_sim3_verified_workspace_bytes.argtypes = [i, i]
+        L.orbgpu_compute_sim3_verified_workspace_bytes.restype = ctypes.c_size_t
+        f = ctypes.c_float
+        L.orbgpu_compute_sim3_verified_batch_device.argtypes = [i, vp, i, vp, vp, vp, vp, i, vp, vp, Sim3RansacParams,
+                                                                f, f, i, i, i, vp, vp, vp, vp, vp]
         _BOUND = True
     return L
 
@@ -124,16 +152,64 @@ class Keyframes:
         return self.tf
 
 
+class KeyframeSearch:
+    """What SearchBySim3 and OptimizeSim3's gathers read of the keyframes of a
+    ``Keyframes`` beyond it (orbgpu_loop_keyframe_search), in HBM.  Host inputs:
+    kps (n_kf, stride) orbgpu.KP_DTYPE (mvKeysUn), mp_desc (n_kf, stride, 32) u8
+    (MapPoint::GetDescriptor per slot), min_dist / max_dist (n_kf, stride) f32,
+    bounds (min_x, max_x, min_y, max_y), scale_factors and inv_level_sigma2
+    (nlevels,) f32, log_scale_factor.  The keypoint descriptors, the pose and
+    the intrinsics are the ``Keyframes``' own."""
+
+    def __init__(self, kfs: "Keyframes", kps, mp_desc, min_dist, max_dist, bounds, scale_factors, inv_level_sigma2,
+                 log_scale_factor, Tcw, K):
+        import torch
+        dev, S, n_kf = kfs.device, kfs.stride, kfs.n_kf
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8) if dt is None  # noqa: E731
+                                            else np.ascontiguousarray(a, dt)).to(dev)
+        self.kps = up(np.ascontiguousarray(kps, orbgpu.KP_DTYPE).reshape(n_kf, S), None)
+        self.mp_desc = up(mp_desc, np.uint8)
+        self.min_dist, self.max_dist = up(min_dist, np.float32), up(max_dist, np.float32)
+        tab = (LoopKeyframeSearch * n_kf)()
+        kpb = orbgpu.KP_DTYPE.itemsize
+        for k in range(n_kf):
+            r, t = tab[k], tab[k].target
+            t.n = int(kfs.counts_host[k])
+            t.kps = self.kps.data_ptr() + kpb * S * k
+            t.desc = kfs.desc.data_ptr() + 32 * S * k
+            t.min_x, t.max_x, t.min_y, t.max_y = (float(v) for v in bounds)
+            t.fx, t.fy, t.cx, t.cy = (float(v) for v in K)
+            t.n_levels = len(scale_factors)
+            t.log_scale_factor = float(log_scale_factor)
+            t.scale_factors[:len(scale_factors)] = [float(v) for v in scale_factors]
+            T = np.eye(4, dtype=np.float32)
+            T[:3, :3] = np.asarray(Tcw[k, :9], np.float32).reshape(3, 3)
+            T[:3, 3] = Tcw[k, 9:12]
+            t.Tcw[:] = [float(v) for v in T.reshape(16)]
+            r.mp_desc = self.mp_desc.data_ptr() + 32 * S * k
+            r.mp_min_dist = self.min_dist.data_ptr() + 4 * S * k
+            r.mp_max_dist = self.max_dist.data_ptr() + 4 * S * k
+            r.inv_level_sigma2[:len(inv_level_sigma2)] = [float(v) for v in inv_level_sigma2]
+        self.d_table = bow.to_device_table(tab, dev)
+
+
 class LoopBurst:
     """ComputeSim3 for `queries` = list of (current_kf, [candidate kfs], rng
     state or seed): all SearchByBoW pairs in one batch, then the Sim3Solver
     set-up and the round-robin RANSAC of every query on the GPU."""
 
     def __init__(self, kfs: Keyframes, queries, nnratio=0.75, check_ori=True, min_matches=20, probability=0.99,
-                 min_inliers=20, max_iterations=300, iterations_per_call=5, fix_scale=False):
+                 min_inliers=20, max_iterations=300, iterations_per_call=5, fix_scale=False, search=None,
+                 match12=None, nmatches=None, th_search=7.5, th2=10.0, min_opt_inliers=20):
+        """search: a KeyframeSearch, needed by step_verified.  match12 (pairs,
+        stride) / nmatches (pairs,): SearchByBoW's results from elsewhere,
+        uploaded instead of computed (no vocabulary needed; search_by_bow and
+        step are then not available)."""
         import torch
-        if kfs.tf is None:
+        if kfs.tf is None and match12 is None:
             raise ValueError("Keyframes.compute_bow() first")
+        self.search = search
+        self.th_search, self.th2, self.min_opt_inliers = th_search, th2, min_opt_inliers
         self.kfs = kfs
         dev = kfs.device
         self.nnratio, self.check_ori, self.min_matches = nnratio, check_ori, min_matches
@@ -155,7 +231,8 @@ class LoopBurst:
         fb = (bow.BowFrame * max(self.n_pairs, 1))()
         ctab = (Sim3Candidate * max(self.n_pairs, 1))()
         for p, (a, b) in enumerate(pairs):
-            fa[p], fb[p] = kfs.frames[a], kfs.frames[b]
+            if kfs.tf is not None:
+                fa[p], fb[p] = kfs.frames[a], kfs.frames[b]
             ctab[p].kf1, ctab[p].kf2 = a, b
         self.d_fa, self.d_fb = bow.to_device_table(fa, dev), bow.to_device_table(fb, dev)
         self.d_cands = bow.to_device_table(ctab, dev)
@@ -171,6 +248,10 @@ class LoopBurst:
                                    device=dev)
         self.states = torch.zeros(P * ctypes.sizeof(Sim3CandidateState), dtype=torch.uint8, device=dev)
         self.inliers = torch.zeros((P, S), dtype=torch.uint8, device=dev)
+        if match12 is not None:
+            self.match.copy_(torch.from_numpy(np.ascontiguousarray(match12, np.int32).reshape(P, S)))
+            self.nmatches.copy_(torch.from_numpy(np.ascontiguousarray(nmatches, np.int32).reshape(P)))
+        self.vstate = None  # the verified loop's state block, results and rows: allocated by step_verified
 
     def search_by_bow(self, stream=None):
         """SearchByBoW(mpCurrentKF, pKF, vpMatches12) for every pair."""
@@ -197,7 +278,56 @@ class LoopBurst:
         self.setup(stream)
         self.compute_sim3(stream)
 
+    def compute_sim3_verified(self, n_passes=1, resume=False, stream=None):
+        """n_passes passes of the verified loop (orbgpu_compute_sim3_verified_batch_device)."""
+        import torch
+        if self.search is None:
+            raise ValueError("LoopBurst(search=KeyframeSearch(...)) is needed for the verified loop")
+        dev, S, Q = self.kfs.device, self.kfs.stride, max(self.n_queries, 1)
+        if self.vstate is None:
+            if resume:
+                raise ValueError("nothing to resume")
+            nbytes = _lib().orbgpu_compute_sim3_verified_workspace_bytes(Q, S)
+            self.vstate = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+            self.vresults = torch.zeros(Q * ctypes.sizeof(ComputeSim3VerifiedResult), dtype=torch.uint8, device=dev)
+            self.vcand_states = torch.zeros(max(self.n_pairs, 1) * ctypes.sizeof(Sim3CandidateState), dtype=torch.uint8,
+                                            device=dev)
+            self.vrows = torch.zeros((Q, 3, S), dtype=torch.int32, device=dev)
+        orbgpu._check(_lib().orbgpu_compute_sim3_verified_batch_device(
+            self.n_queries, self.d_queries.data_ptr(), self.n_pairs, self.d_cands.data_ptr(),
+            self.kfs.d_table.data_ptr(), self.search.d_table.data_ptr(), self.match.data_ptr(), S,
+            self.workspace.data_ptr(), self.n_corr.data_ptr(), self.params, self.th_search, self.th2,
+            self.min_opt_inliers, int(n_passes), int(bool(resume)), self.vstate.data_ptr(), self.vresults.data_ptr(),
+            self.vcand_states.data_ptr(), self.vrows.data_ptr(), orbgpu._stream_ptr(stream)),
+            "orbgpu_compute_sim3_verified_batch_device")
+
+    def step_verified(self, n_passes=1, stream=None, max_calls=1 << 20):
+        """The reference's whole loop for every query: the Sim3Solver set-up
+        (after SearchByBoW unless match12 was uploaded), then calls of n_passes
+        passes each until no query is PENDING.  Returns the number of calls."""
+        if self.kfs.tf is not None:
+            self.search_by_bow(stream)
+        self.setup(stream)
+        calls = 0
+        while calls < max_calls:
+            self.compute_sim3_verified(n_passes, resume=calls > 0, stream=stream)
+            calls += 1
+            if not any(r.status == PENDING for r in self.verified_results()):
+                break
+        return calls
+
     # ---- results (host) ---------------------------------------------------
+    def verified_results(self):
+        return _struct_rows(self.vresults, ComputeSim3VerifiedResult, self.n_queries)
+
+    def verified_candidate_states(self):
+        return _struct_rows(self.vcand_states, Sim3CandidateState, self.n_pairs)
+
+    def verified_rows(self):
+        """(n_queries, 3, stride) int32 of each query's last verification, by
+        KF1 slot: vbInliers, SearchBySim3's agreed row, the final matches."""
+        return self.vrows[:self.n_queries].cpu().numpy()
+
     def query_results(self):
         return _struct_rows(self.results, ComputeSim3Result, self.n_queries)
 
