@@ -12,12 +12,14 @@
 #include <cstdint>
 
 #include "../../include/orbgpu_loop.h"
+#include "ransac_device.h"
 #include "sim3_device.h"
 
 namespace orbgpu {
 namespace loopdev {
 
 using namespace sim3dev;
+using namespace ransacdev;
 
 #ifndef ORBGPU_SIM3_THREADS
 #define ORBGPU_SIM3_THREADS 512
@@ -35,8 +37,6 @@ struct Workspace {  // SoA, candidate c at c * stride
     float2* P1;     // mvP1im1 / mvP2im2: FromCameraToImage of X1 / X2 (the ctor's, Sim3Solver.cpp:97-98)
     float2* P2;
 };
-
-__host__ __device__ inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 __host__ __device__ inline Workspace carve(void* base, int n_cand, int stride) {
     const size_t n = (size_t)n_cand * stride;
@@ -63,25 +63,6 @@ inline size_t workspace_bytes(int n_cand, int stride) {
     return 2 * align256(n * 12) + 3 * align256(n * 4) + 2 * align256(n * 8);
 }
 
-// glibc random_r TYPE_3 step (csrc/ransac.cpp restates the same generator):
-// returns the raw sum written into the state; rand() is raw >> 1
-__device__ inline uint32_t rand_next_raw(int32_t* r, int& f, int& b) {
-    const uint32_t val = (uint32_t)r[f] + (uint32_t)r[b];
-    r[f] = (int32_t)val;
-    if (++f >= 31) {
-        f = 0;
-        ++b;
-    } else if (++b >= 31) {
-        b = 0;
-    }
-    return val;
-}
-
-// DUtils::Random::RandomInt(0, d-1)
-__device__ inline int random_below(int32_t v, int d) {
-    return (int)(((double)v / ((double)2147483647 + 1.0)) * d);
-}
-
 // Sim3Solver::SetRansacParameters (Sim3Solver.cpp:111-141): mRansacMaxIts of a solver with N
 // correspondences (0 for N < 0, no solver)
 __device__ inline int ransac_max_iterations(int N, const orbgpu_sim3_ransac_params& prm) {
@@ -92,43 +73,16 @@ __device__ inline int ransac_max_iterations(int N, const orbgpu_sim3_ransac_para
         if (prm.min_inliers == N) {
             n_it = 1;
         } else {
-            const double v = ceil(log(1.0 - prm.probability) / log(1.0 - pow((double)eps, 3.0)));
-            // an out-of-range double -> int conversion is INT_MIN on x86 (cvttsd2si)
-            n_it = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (int)0x80000000;
+            n_it = ransac_iterations(prm.probability, eps);
         }
         max_its = max(1, min(n_it, prm.max_iterations));
     }
     return max_its;
 }
 
-// one hypothesis' minimal set: vAvailableIndices = mvAllIndices; 3 x RandomInt + swap-remove
-// (Sim3Solver.cpp:172-183) over N correspondences.  gen[0..2] = the raw values drawn.
+// one hypothesis' minimal set (Sim3Solver.cpp:172-183): three swap-remove draws
 __device__ __forceinline__ void draw_triplet(int N, int32_t* s_r, int& rf, int& rb, int32_t* gen, int* trip) {
-    int pos[2], val[2], nmod = 0;
-    for (int d = 0; d < 3; ++d) {
-        const int size = N - d;
-        const uint32_t raw = rand_next_raw(s_r, rf, rb);
-        gen[d] = (int32_t)raw;
-        const int r = random_below((int32_t)(raw >> 1), size);
-        int idx = r;  // vAvailableIndices[r] after the earlier swaps
-        for (int m = nmod - 1; m >= 0; --m)
-            if (pos[m] == r) {
-                idx = val[m];
-                break;
-            }
-        int back = size - 1;  // vAvailableIndices.back()
-        for (int m = nmod - 1; m >= 0; --m)
-            if (pos[m] == size - 1) {
-                back = val[m];
-                break;
-            }
-        trip[d] = idx;
-        if (d < 2) {
-            pos[nmod] = r;
-            val[nmod] = back;
-            ++nmod;
-        }
-    }
+    draw_set<3>(N, s_r, rf, rb, gen, trip);
 }
 
 // CheckInliers of hypothesis H (and Hb when two) over one candidate's N correspondences at

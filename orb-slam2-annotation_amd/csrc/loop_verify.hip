@@ -76,13 +76,6 @@ struct VState {  // the opaque block, carved
     uint8_t* removed;
 };
 
-template <class T>
-__host__ __device__ inline T* take(char*& p, size_t count) {
-    T* r = reinterpret_cast<T*>(p);
-    p += align256(count * sizeof(T));
-    return r;
-}
-
 __host__ __device__ inline VState carve_state(void* base, int nq, int stride, size_t* bytes) {
     const size_t Q = (size_t)(nq > 0 ? nq : 1), S = (size_t)(stride > 0 ? stride : 1);
     char* p = static_cast<char*>(base);
@@ -376,16 +369,6 @@ __global__ __launch_bounds__(kQThreads) void compute_sim3_resume_kernel(
 
 // ------------------------------------------------------------------ the verification
 
-// an idle query's calls: no keypoints, no points (proj_kernel then writes only its count)
-__device__ inline void idle_call(orbgpu_proj_call& c) {
-    int* w = reinterpret_cast<int*>(&c);
-    for (int k = 0; k < (int)(sizeof(orbgpu_proj_call) / 4); ++k) w[k] = 0;
-    c.variant = ORBGPU_PROJ_SIM3_DIR;
-    c.target.n_levels = 1;
-    c.target.max_x = 1.f;
-    c.target.max_y = 1.f;
-}
-
 __global__ __launch_bounds__(kVThreads) void verify_prep_kernel(
     const orbgpu_compute_sim3_query* __restrict__ queries, const orbgpu_sim3_candidate* __restrict__ cands,
     const orbgpu_loop_keyframe* __restrict__ kfs, const orbgpu_loop_keyframe_search* __restrict__ kss,
@@ -394,7 +377,7 @@ __global__ __launch_bounds__(kVThreads) void verify_prep_kernel(
     const QState& S = V.q[q];
     orbgpu_proj_call* calls = V.calls + 2 * (size_t)q;
     if (!S.verify) {
-        if (tid < 2) idle_call(calls[tid]);
+        if (tid < 2) idle_call(calls[tid], ORBGPU_PROJ_SIM3_DIR);
         return;
     }
     const int c = S.last_c, gc = queries[q].first_cand + c;
@@ -456,7 +439,7 @@ __global__ __launch_bounds__(kVThreads) void verify_prep_kernel(
         const orbgpu_loop_keyframe& KA = dir == 0 ? K1 : K2;
         const orbgpu_proj_target& T1 = kss[cd.kf1].target;
         orbgpu_proj_call& k = calls[dir];
-        idle_call(k);
+        idle_call(k, ORBGPU_PROJ_SIM3_DIR);
         k.th = th_search;
         k.target = B.target;
         k.target.u_right = nullptr;
