@@ -136,10 +136,17 @@ def _hamming(a, b):
 
 
 def search_by_projection(variant, tgt, pts, th, nnratio=0.6, check_ori=True, orb_dist=50, mono=True,
-                         last_Tcw=None):
+                         last_Tcw=None, trace=None):
     """The four SearchByProjection overloads (M:63-155, 352-470, 1506-1641,
     1661-1790).  Returns (nmatches, match) with match per target keypoint:
-    point index, -1 untouched, -2 set to NULL by the rotation cull."""
+    point index, -1 untouched, -2 set to NULL by the rotation cull.
+
+    trace: a list that receives one dict per point reaching the candidate
+    loop: ip, cands (GetFeaturesInArea's, in order), passed [(keypoint,
+    Hamming distance, octave)] for the candidates that pass every filter but
+    occupancy, hidden (those of `passed` that occupancy hides at this point's
+    turn), slot (the keypoint assigned, or None) and bin (its rotation bin
+    when the histogram is kept, else None).  The results do not depend on it."""
     k = tgt["kps"]
     n = len(k)
     grid = Grid(tgt)
@@ -241,11 +248,13 @@ def search_by_projection(variant, tgt, pts, th, nnratio=0.6, check_ori=True, orb
         d = pts["desc"][ip]
         best, best_i, best_l = 256, -1, -1
         best2, best_l2 = 256, -1
+        rec = None
+        if trace is not None:
+            rec = {"ip": ip, "cands": list(cands), "passed": [], "hidden": [], "slot": None, "bin": None}
+            trace.append(rec)
         for i in cands:
-            if variant in (LOCAL, LAST_FRAME):
-                if occ[i] == 2:
-                    continue
-            elif occ[i]:
+            hid = occ[i] == 2 if variant in (LOCAL, LAST_FRAME) else bool(occ[i])
+            if hid and rec is None:
                 continue
             if variant == SIM3 and not (lvl_lo <= int(k["octave"][i]) <= lvl_hi):
                 continue
@@ -253,6 +262,11 @@ def search_by_projection(variant, tgt, pts, th, nnratio=0.6, check_ori=True, orb
                 if abs(f32(ur - f32(uR[i]))) > srad:
                     continue
             dist = _hamming(d, tgt["desc"][i])
+            if rec is not None:
+                rec["passed"].append((i, dist, int(k["octave"][i])))
+                if hid:
+                    rec["hidden"].append(i)
+                    continue
             if dist < best:
                 best2, best_l2 = best, best_l
                 best, best_i, best_l = dist, i, int(k["octave"][i])
@@ -275,6 +289,8 @@ def search_by_projection(variant, tgt, pts, th, nnratio=0.6, check_ori=True, orb
         match[best_i] = ip
         occ[best_i] = 2 if fl & HAS_OBS else 1
         nm += 1
+        if rec is not None:
+            rec["slot"] = best_i
         if check_ori and variant in (LAST_FRAME, KEYFRAME):
             rot = f32(f32(pts["angle"][ip]) - f32(k["angle"][best_i]))
             if rot < f32(0.0):
@@ -283,6 +299,8 @@ def search_by_projection(variant, tgt, pts, th, nnratio=0.6, check_ori=True, orb
             if b == HL:
                 b = 0
             hist[b].append(best_i)
+            if rec is not None:
+                rec["bin"] = b
     if check_ori and variant in (LAST_FRAME, KEYFRAME):
         m1 = m2 = m3 = 0
         i1 = i2 = i3 = -1
@@ -310,13 +328,14 @@ def search_by_projection(variant, tgt, pts, th, nnratio=0.6, check_ori=True, orb
 FUSE, FUSE_SIM3, SIM3_DIR = 4, 5, 6
 
 
-def radius_search(variant, tgt, pts, th, last_Tcw=None):
+def radius_search(variant, tgt, pts, th, last_Tcw=None, trace=None):
     """The per-point searches: Fuse(pKF, vpMapPoints, th) (M:962-1115, FUSE),
     Fuse(pKF, Scw, vpPoints, th, vpReplace) (M:1119-1249, FUSE_SIM3) and one
     direction of SearchBySim3 (M:1305-1387, SIM3_DIR: last_Tcw = the points'
     own keyframe pose, tgt Tcw = [sR|t], tgt fx..cy = pKF1's).  Returns
     (count, best) with best[i] = the target keypoint of point i when its
-    distance is <= TH_LOW (Fuse) / TH_HIGH (SearchBySim3), else -1."""
+    distance is <= TH_LOW (Fuse) / TH_HIGH (SearchBySim3), else -1.  trace: as
+    in search_by_projection (nothing is ever hidden here; bin stays None)."""
     k = tgt["kps"]
     grid = Grid(tgt)
     uR = tgt.get("u_right")
@@ -371,6 +390,10 @@ def radius_search(variant, tgt, pts, th, last_Tcw=None):
         rad = f32(f32(th) * sf[lvl])
         cands = grid.area(u, v, rad)
         best, best_i = 1 << 30, -1
+        rec = None
+        if trace is not None and cands:
+            rec = {"ip": ip, "cands": list(cands), "passed": [], "hidden": [], "slot": None, "bin": None}
+            trace.append(rec)
         for i in cands:
             o = int(k["octave"][i])
             if o < lvl - 1 or o > lvl:
@@ -386,10 +409,14 @@ def radius_search(variant, tgt, pts, th, last_Tcw=None):
                 elif f64(f32(e2 * isig[o & 15])) > 5.99:
                     continue
             d = _hamming(pts["desc"][ip], tgt["desc"][i])
+            if rec is not None:
+                rec["passed"].append((i, d, o))
             if d < best:
                 best, best_i = d, i
         if best_i >= 0 and best <= limit:
             best_out[ip] = best_i
+            if rec is not None:
+                rec["slot"] = best_i
     return int((best_out >= 0).sum()), best_out
 
 

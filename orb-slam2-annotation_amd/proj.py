@@ -96,6 +96,52 @@ def search_by_projection(variant, tgt, pts, th, nnratio=0.6, check_ori=True, orb
     return nm.value, match[:n]
 
 
+def search_by_projection_batch(calls, stride, fill=-7):
+    """Several calls in one launch of orbgpu_search_by_projection_batch_device.  calls: a list of
+    dicts with variant, tgt, pts, th and optionally nnratio, check_ori, orb_dist, mono, last_Tcw
+    (the arguments of search_by_projection).  Nothing is checked on the host: the kernel rejects
+    a call whose output does not fit `stride` or whose target exceeds its capacity.  Returns
+    (nmatches[ncalls], match[ncalls, stride]), every output word `fill` before the launch."""
+    import torch
+    held = []
+
+    def dev(a, dtype):
+        if a is None:
+            return None
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype).reshape(-1).view(np.uint8).copy()).cuda()
+        held.append(t)
+        return t.data_ptr() if t.numel() else None
+
+    arr = (Call * max(len(calls), 1))()
+    for C, c in zip(arr, calls):
+        C.variant, C.th = int(c["variant"]), float(c["th"])
+        C.check_ori, C.nnratio = int(c.get("check_ori", True)), float(c.get("nnratio", 0.6))
+        C.orb_dist, C.mono = int(c.get("orb_dist", 50)), int(c.get("mono", True))
+        if c.get("last_Tcw") is not None:
+            C.last_Tcw[:] = [float(v) for v in np.asarray(c["last_Tcw"], np.float32).reshape(16)]
+        keep = []
+        C.target, C.points = _target(c["tgt"], keep), _points(c["pts"], keep)
+        t, p = c["tgt"], c["pts"]
+        C.target.kps = dev(t["kps"], orbgpu.KP_DTYPE)
+        C.target.desc = dev(t["desc"], np.uint8)
+        C.target.u_right = dev(t.get("u_right"), np.float32)
+        C.target.occupied = dev(t.get("occupied"), np.uint8)
+        C.points.flags = dev(p["flags"], np.int32)
+        C.points.desc = dev(p["desc"], np.uint8)
+        for f, dt in (("pos", np.float32), ("normal", np.float32), ("min_dist", np.float32),
+                      ("max_dist", np.float32), ("octave", np.int32), ("angle", np.float32),
+                      ("track", np.float32), ("track_level", np.int32)):
+            setattr(C.points, f, dev(p.get(f), dt))
+    d_calls = torch.from_numpy(np.frombuffer(bytes(arr), np.uint8).copy()).cuda()
+    match = torch.full((len(calls), stride), fill, dtype=torch.int32, device="cuda")
+    nm = torch.full((max(len(calls), 1),), fill, dtype=torch.int32, device="cuda")
+    orbgpu._check(orbgpu.lib().orbgpu_search_by_projection_batch_device(
+        len(calls), vp(d_calls.data_ptr()), int(stride), vp(match.data_ptr()), vp(nm.data_ptr()), None),
+        "orbgpu_search_by_projection_batch_device")
+    torch.cuda.synchronize()
+    return nm.cpu().numpy()[:len(calls)], match.cpu().numpy()
+
+
 def radius_search(variant, tgt, pts, th, last_Tcw=None):
     """FUSE / FUSE_SIM3 / SIM3_DIR: (count, best keypoint per point or -1)."""
     return search_by_projection(variant, tgt, pts, th, last_Tcw=last_Tcw)
@@ -123,8 +169,10 @@ def search_by_sim3(kf1, kf2, pts1, pts2, s12, R12, t12, th):
     return nf.value, match[:n1]
 
 
-def is_in_frustum(tgt, pts, cos_limit):
-    """Frame::isInFrustum on the GPU for every point: (flags, track, level)."""
+def is_in_frustum(tgt, pts, cos_limit, track0=None, level0=None):
+    """Frame::isInFrustum on the GPU for every point: (flags, track, level).  track0 (n, 4) and
+    level0 (n): what the track and level arrays hold before the call (zeros when left out);
+    the rows of points that are not in view keep it."""
     import torch
     keep = []
     T = _target(tgt, keep)
@@ -133,8 +181,9 @@ def is_in_frustum(tgt, pts, cos_limit):
     pos, nrm = dev(pts["pos"], np.float32), dev(pts["normal"], np.float32)
     mind, maxd = dev(pts["min_dist"], np.float32), dev(pts["max_dist"], np.float32)
     flags = dev(pts["flags"], np.int32)
-    track = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
-    level = torch.zeros(n, dtype=torch.int32, device="cuda")
+    track = dev(track0, np.float32).reshape(n, 4) if track0 is not None else \
+        torch.zeros((n, 4), dtype=torch.float32, device="cuda")
+    level = dev(level0, np.int32) if level0 is not None else torch.zeros(n, dtype=torch.int32, device="cuda")
     orbgpu._check(orbgpu.lib().orbgpu_is_in_frustum_device(ctypes.byref(T), n, pos.data_ptr(), nrm.data_ptr(),
                                                           mind.data_ptr(), maxd.data_ptr(), float(cos_limit),
                                                           flags.data_ptr(), track.data_ptr(), level.data_ptr(), None),
