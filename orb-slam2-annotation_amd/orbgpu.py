@@ -151,6 +151,11 @@ def lib() -> ctypes.CDLL:
         # orbgpu_sim3opt.h
         L.orbgpu_optimize_sim3_batch_device.argtypes = [i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbgpu_optimize_sim3_batch.argtypes = [i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
+        # orbgpu_localba.h
+        L.orbgpu_local_ba_workspace_bytes.argtypes = [i, i, i, i, i]
+        L.orbgpu_local_ba_workspace_bytes.restype = sz
+        L.orbgpu_local_ba_batch_device.argtypes = [i, vp, i, i, i, i, i] + [vp] * 13 + [sz, vp]
+        L.orbgpu_local_ba_batch.argtypes = [i, vp, i, i, i, i, i] + [vp] * 13 + [sz]
         # orbgpu_ransac.h
         L.orbgpu_srand.argtypes = [ctypes.c_uint]
         L.orbgpu_srand.restype = None

@@ -973,3 +973,86 @@ def sim3opt_scene(n: int, seed: int, outliers: float = 0.2, fix_scale: bool = Fa
             "obs1": f32(obs1), "obs2": f32(obs2), "inv_sigma2_1": f32(1.0 / 1.2 ** (2.0 * oct1)),
             "inv_sigma2_2": f32(1.0 / 1.2 ** (2.0 * oct2)), "K1": tuple(K), "K2": tuple(K), "th2": float(th2),
             "fix_scale": bool(fix_scale), "outlier": is_out, "R_true": R, "t_true": t, "s_true": s}
+
+
+def localba_scene(n_local: int, n_fixed: int, n_points: int, seed: int, stereo: float = 0.0, noise: float = 1.0,
+                  outliers: float = 0.0, start_rot: float = 0.01, start_t: float = 0.03, start_pt: float = 0.05,
+                  kf0_local: bool = False, single_obs: int = 0, behind: bool = False, min_obs: int = 2,
+                  see: float = 0.7):
+    """A job for Optimizer::LocalBundleAdjustment: n_local + n_fixed cameras on
+    an arc, all looking at a cloud of n_points MapPoints 2-12 m away; each point
+    is seen by a random subset of the cameras (each with probability `see`, at
+    least `min_obs` of them; the first `single_obs` points by exactly one local
+    camera).  Keypoints at octaves 0-7 with Gaussian noise of `noise` pixels
+    times the level's scale factor, a fraction `stereo` of the observations
+    with a right coordinate, a fraction `outliers` of them 30-80 px off.  The
+    local poses start `start_rot` rad / `start_t` m from the truth, the points
+    `start_pt` m; fixed poses start at the truth.  `kf0_local` sets the first
+    local pose's fixed flag (it then starts at the truth too).  `behind` moves
+    the start of point 0 behind the first camera that sees it (mirrored
+    through the camera centre), observation kept.  Edges are grouped by point, cameras ascending within a point.
+    Returns dict(Tcw (P, 4, 4), Tcw_true, fixed (P uint8), cam (P, 5) = fx, fy,
+    cx, cy, bf, Xw (M, 3), Xw_true, pose_idx, point_idx (E int32), obs (E, 3),
+    inv_sigma2 (E), outlier (E bool, injected), n_local)."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, bf = 517.306408, 516.469215, 318.643040, 255.313989, 40.0
+    P, M = n_local + n_fixed, n_points
+    centre = np.array([0.0, 0.0, 7.0])
+    X = centre + rng.uniform(-1.0, 1.0, (M, 3)) * np.array([3.0, 2.0, 4.0])
+    T_true = np.zeros((P, 4, 4))
+    for p in range(P):
+        a = (p - 0.5 * (P - 1)) * (0.5 / max(P - 1, 1))  # half a radian of arc around the cloud's centre
+        c = centre + 7.0 * np.array([np.sin(a), 0.05 * rng.normal(), -np.cos(a)])
+        zc = centre - c
+        zc /= np.linalg.norm(zc)
+        xc = np.cross(np.array([0.0, 1.0, 0.0]), zc)
+        xc /= np.linalg.norm(xc)
+        R = np.stack([xc, np.cross(zc, xc), zc]) @ _rodrigues(rng.normal(size=3) * 0.02)
+        T_true[p] = np.eye(4)
+        T_true[p, :3, :3], T_true[p, :3, 3] = R, -R @ c
+    fixed = np.zeros(P, np.uint8)
+    fixed[n_local:] = 1
+    if kf0_local and n_local:
+        fixed[0] = 1
+    T0 = T_true.copy()
+    for p in range(P):
+        if not fixed[p]:
+            d = rng.normal(size=(2, 3))
+            d /= np.linalg.norm(d, axis=1, keepdims=True)
+            dR = _rodrigues(d[0] * start_rot)
+            T0[p, :3, :3], T0[p, :3, 3] = dR @ T_true[p, :3, :3], dR @ T_true[p, :3, 3] + d[1] * start_t
+    pose_idx, point_idx = [], []
+    for m in range(M):
+        if m < single_obs and n_local:
+            cams = [int(rng.integers(0, n_local))]
+        else:
+            sees = rng.uniform(size=P) < see
+            need = min(min_obs, P) - int(sees.sum())
+            if need > 0:
+                sees[rng.choice(np.nonzero(~sees)[0], need, replace=False)] = True
+            cams = list(np.nonzero(sees)[0])
+        pose_idx += cams
+        point_idx += [m] * len(cams)
+    pose_idx, point_idx = np.asarray(pose_idx, np.int32), np.asarray(point_idx, np.int32)
+    E = len(pose_idx)
+    Xc = np.einsum("eij,ej->ei", T_true[pose_idx, :3, :3], X[point_idx]) + T_true[pose_idx, :3, 3]
+    u, v, z = fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy, Xc[:, 2]
+    octave = rng.integers(0, 8, E)
+    # a right coordinate only where it stays well inside the image (a negative one means monocular)
+    is_st = (rng.uniform(size=E) < stereo) & (u - bf / z > 20.0)
+    is_out = rng.uniform(size=E) < outliers
+    du = rng.normal(size=(E, 3)) * (noise * 1.2 ** octave)[:, None]
+    ang, off = rng.uniform(0, 2 * np.pi, E), rng.uniform(30, 80, E)
+    du[is_out, 0] += (off * np.cos(ang))[is_out]
+    du[is_out, 1] += (off * np.sin(ang))[is_out]
+    obs = np.stack([u + du[:, 0], v + du[:, 1], np.where(is_st, u - bf / z + du[:, 2], -1.0)], 1)
+    X0 = X + rng.normal(size=(M, 3)) * start_pt
+    if behind and E:  # mirrored through the camera centre: the same monocular projection, z < 0
+        p = int(pose_idx[np.nonzero(point_idx == 0)[0][0]])
+        Xc_b = -(T_true[p, :3, :3] @ X[0] + T_true[p, :3, 3])
+        X0[0] = T_true[p, :3, :3].T @ (Xc_b - T_true[p, :3, 3])
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    return {"Tcw": f32(T0), "Tcw_true": f32(T_true), "fixed": fixed,
+            "cam": f32(np.tile([fx, fy, cx, cy, bf], (P, 1))), "Xw": f32(X0), "Xw_true": f32(X),
+            "pose_idx": pose_idx, "point_idx": point_idx, "obs": f32(obs),
+            "inv_sigma2": f32(1.0 / 1.2 ** (2.0 * octave)), "outlier": is_out, "n_local": n_local}
