@@ -27,8 +27,9 @@ int orbgpu_debug_level_octree(orbgpu_extractor* ex, int frame, int level, int* x
 int orbgpu_debug_level_blur(orbgpu_extractor* ex, int frame, int level, uint8_t* dst, size_t dst_step);
 
 /* Per-pass trace of the octree kernel for frame 0 (enable before extracting;
- * out: per level 512 ints = [passes, 0, then 8 ints per pass: inner, nL, C,
- * S, nToExpand, kstop, nkeys, N]). */
+ * out: per level 512 ints = [passes, fused, then 8 ints per pass: inner, nL,
+ * C, S, nToExpand, kstop, nkeys, N]; fused = 1 + the main passes taken from
+ * the one key sweep, 0 for a level that went pass by pass). */
 int orbgpu_debug_octree_trace(orbgpu_extractor* ex, int enable, int* out, int cap);
 
 /* CPU run of the fused pyramid pass's plan (pyramid_plan.cpp), no GPU
@@ -42,6 +43,12 @@ int orbgpu_debug_octree_trace(orbgpu_extractor* ex, int enable, int* out, int ca
  * entries per compute lane, LDS bytes per block, level-0 ring rows}. */
 int orbgpu_debug_pyramid_emulate(int nfeatures, float scale_factor, int nlevels, int width, int height,
                                  const uint8_t* img, size_t img_step, uint8_t* out, size_t out_bytes, int* info);
+
+/* The octree launch's plan for these parameters (no GPU needed): for each of
+ * the two level groups, out[5 g .. 5 g + 4] = {first level, levels, keys held
+ * in LDS, nodes held in LDS, LDS bytes per workgroup}; the launch takes the
+ * larger group's LDS. */
+int orbgpu_debug_octree_plan(int nfeatures, float scale_factor, int nlevels, int width, int height, int* out);
 
 /* The fused pyramid plan's work per tick (no GPU; tools/pyr_plan_cost.py):
  * rows[k * lanes + i] = output rows compute lane i (entry 0, then entry 1 at

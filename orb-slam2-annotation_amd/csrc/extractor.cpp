@@ -49,6 +49,10 @@ bool single_done_flag() { return ORB_ENV_ONCE_FLAG("ORBGPU_SINGLE_DONE_FLAG", tr
 // allocation the device refuses: the pinned staging and the copy kernel.
 bool single_vram_staging() { return ORB_ENV_ONCE_FLAG("ORBGPU_SINGLE_VRAM_STAGING", true); }
 
+// ORBGPU_OCT_FUSED=0 selects the octree's pass-by-pass main loop (A/B and parity
+// checks); read per batch: tests/test_octree_fused.py switches it in-process
+bool oct_fused() { return env_now_int("ORBGPU_OCT_FUSED", 1) != 0; }
+
 // ORBGPU_PYR_BANDS=0 selects the level-by-level launches (A/B and parity checks)
 bool pyr_bands_off() { return !ORB_ENV_ONCE_FLAG("ORBGPU_PYR_BANDS", true); }
 
@@ -83,7 +87,7 @@ int run_batch(orbgpu_extractor* e, const uint8_t* imgs, int batch, size_t row_st
     const int nch = (err_copy || batch < 16 * od_chunks()) ? 1 : od_chunks();
     if (nch == 1) {
         ORB_HIP(launch_octree(g, batch, e->d_cand, e->d_cell_counts, e->d_gkeys, e->d_gknode, e->d_oct_out,
-                              e->d_oct_count, e->d_err, e->geo.oct_groups, 2, e->d_trace, s));
+                              e->d_oct_count, e->d_err, e->geo.oct_groups, 2, e->d_trace, oct_fused(), s));
         if (evs) ORB_HIP(hipEventRecord(evs[3], s));
         if (e->stage_ev[2]) ORB_HIP(hipEventRecord(e->stage_ev[2], s));
         // GaussianBlur is fused into describe (blur of each keypoint's patch);
@@ -107,7 +111,7 @@ int run_batch(orbgpu_extractor* e, const uint8_t* imgs, int batch, size_t row_st
                                   e->d_cell_counts + (size_t)f0 * g.total_cells,
                                   e->d_gkeys + (size_t)f0 * g.cand_frame, e->d_gknode + (size_t)f0 * g.cand_frame,
                                   e->d_oct_out + (size_t)f0 * g.slots_frame, e->d_oct_count + (size_t)f0 * kOcStride,
-                                  e->d_err, e->geo.oct_groups, 2, c == 0 ? e->d_trace.get() : nullptr, s));
+                                  e->d_err, e->geo.oct_groups, 2, c == 0 ? e->d_trace.get() : nullptr, oct_fused(), s));
             // the octree stage ends with the last chunk's octree (the describes of the
             // earlier chunks overlap it on the aux stream; describe = the rest)
             if (c == nch - 1 && evs) ORB_HIP(hipEventRecord(evs[3], s));

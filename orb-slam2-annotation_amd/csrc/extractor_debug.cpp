@@ -130,6 +130,24 @@ int orbgpu_debug_pyramid_emulate(int nfeatures, float scale_factor, int nlevels,
     return ORBGPU_OK;
 }
 
+// The octree launch's plan for these parameters (no GPU): per level group its
+// first level, level count, keys and nodes held in LDS, and LDS bytes.
+int orbgpu_debug_octree_plan(int nfeatures, float scale_factor, int nlevels, int width, int height, int* out) {
+    if (!out || nfeatures <= 0 || nlevels <= 0 || nlevels > kMaxLevels || !(scale_factor > 1.f) || width <= 0 ||
+        height <= 0)
+        return fail(ORBGPU_ERR_ARG, "invalid octree plan arguments");
+    ExtractorGeometry geo;  // host geometry only: no device is touched
+    GeometryTables t;
+    const int rc = plan_geometry(nfeatures, scale_factor, nlevels, width, height, geo, t);
+    if (rc) return rc;
+    for (int i = 0; i < 2; ++i) {
+        const OctreeGroup& G = geo.oct_groups[i];
+        const int v[5] = {G.level0, G.nlev, G.kcap, G.ncap, (int)octree_lds_bytes(geo.g, G.kcap, G.ncap)};
+        std::memcpy(out + 5 * i, v, sizeof(v));
+    }
+    return ORBGPU_OK;
+}
+
 // The fused pyramid plan's work per tick (tools/pyr_plan_cost.py): rows[k *
 // lanes + i] = the rows lane i (entry 0, then entry 1 at i + CL) computes at
 // tick k; lane_info[i] = level | tail << 8 (level 0: an idle lane); dims =

@@ -15,6 +15,9 @@
 //     that makes the list reach N -- found with a prefix sum of (children-1);
 //   * each key carries its node index; a pass is two sweeps over the keys
 //     (quadrant histogram via LDS atomics, then remap to the child/new slot);
+//   * the first three main passes are taken together (ORBGPU_OCT_FUSED, on by
+//     default): one sweep counts the keys per (root, three-quadrant path), one
+//     wave replays the passes on the counts, one sweep remaps the keys;
 //   * finally the max-response key per node (first in candidate order on
 //     ties, :751-767) via one LDS atomicMax of (score << 24 | ~index).
 // The reference breaks size ties by heap address (:690); here ties are
@@ -298,12 +301,175 @@ __device__ void wave_small_pass(const ONode* old, ONode* nw, unsigned long long*
         for (int i = lane; i < nNew; i += 64) s_aux0[i] = 0;
 }
 
+// ---- the first three main passes from one key sweep -----------------------
+// The main passes are a fixed function of the keys: a node's child boxes follow
+// from its own box (child_rect), so a key's way down three subdivisions below
+// its root is three node_quad tests against nested boxes, and everything the
+// list logic needs is the key count of each (root, path).  A node at depth d
+// is named by gid_d = root * 4^d + its d path digits (first digit highest), so
+// its children are gid_d * 4 + q and the keys below it are the depth-3 bins
+// [gid_d << 2(3-d), (gid_d + 1) << 2(3-d)).
+// Scratch (over the quadrant counters, aux0, aux1 and the flags, which are idle
+// between the roots phase and the first per-pass pass), for up to kFusedRoots
+// roots: the counts by depth -- [0, 64R) depth 3, [64R, 80R) depth 2,
+// [80R, 84R) depth 1 --, the bin -> final list position table, and the gid tags
+// (gid | depth << 12) of the two node lists.
+constexpr int kFusedRoots = 4;
+constexpr int kFusedTabOfs = kFusedRoots * 84 * 4;             // u16[64 R]
+constexpr int kFusedTagOfs = kFusedTabOfs + kFusedRoots * 64 * 2;  // 2 x u16[256]: a pass of <= 64 nodes makes <= 256
+constexpr int kFusedBytes = kFusedTagOfs + 2 * 256 * 2;
+static_assert(kFusedBytes % 16 == 0, "the key region behind the fused scratch stays 16-byte aligned");
+
+// One sweep: every key's depth-3 bin (kept as its node word until the remap)
+// and the bins' counts.  Keys come in candidate order (cell by cell), so the
+// keys of neighbouring lanes mostly share a bin: the first lane of each run of
+// equal bins adds the run's length -- one LDS atomic per run, not per key.
+template <int NT, class KS>
+__device__ void fused_sweep(const KS& ks, const ONode* roots, int* s_bins, int nk) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int k0 = tid & ~63; k0 < nk; k0 += NT) {  // wave-uniform: every lane takes part in the ballot
+        const int k = k0 + lane;
+        const bool valid = k < nk;
+        int bin = -1;
+        if (valid) {
+            const int r = ks.node(k);
+            const uint32_t key = ks.key(k);
+            ONode nd = roots[r];
+            const int q1 = node_quad(nd, key);
+            nd = child_rect(nd, q1);
+            const int q2 = node_quad(nd, key);
+            nd = child_rect(nd, q2);
+            const int q3 = node_quad(nd, key);
+            bin = (r << 6) | (q1 << 4) | (q2 << 2) | q3;
+            ks.set_node(k, bin);
+        }
+        const int prev = __shfl_up(bin, 1);
+        const bool head = lane == 0 || bin != prev;  // (the lanes past nk: one run of bin -1)
+        const unsigned long long rest = (__ballot(head) >> lane) >> 1;
+        const int len = rest ? (int)__builtin_ctzll(rest) + 1 : 64 - lane;
+        if (head && valid) atomicAdd(&s_bins[bin], len);
+    }
+}
+
+// Wave 0 replays main passes 1..3 on the counts (lane = node): children pushed
+// to the front in reverse push order, empty children dropped, nodes with one
+// key kept, creation order -- as a main pass of wave_small_pass, with the child
+// counts read from the depth sums instead of a quadrant histogram.  The replay
+// stops before a pass that the general code has to run itself: the pass that
+// ends the distribution (:673), one that overflows a capacity (it reports the
+// error), or a list of more than 64 nodes; and after the pass at which the
+// reference switches to its finishing loop (:678).  Then it fills the table
+// bin -> list position of the node that holds the bin, and publishes the pass
+// state in s_misc[27..31]: list size, buffer, next seq, inner, passes done.
+__device__ inline void wave_replay(ONode* s_node0, ONode* s_node1, uint8_t* s_fused, int* s_misc, int nroots, int nini,
+                                   int N, int ncap, int nk, int l, int f, int* trace, int lane) {
+    int* s_bins = reinterpret_cast<int*>(s_fused);
+    uint16_t* s_tab = reinterpret_cast<uint16_t*>(s_fused + kFusedTabOfs);
+    uint16_t* s_tag = reinterpret_cast<uint16_t*>(s_fused + kFusedTagOfs);
+    // the counts at depth 2 and 1 are sums of the depth-3 bins
+    int* A3 = s_bins;
+    int* A2 = s_bins + nroots * 64;
+    int* A1 = s_bins + nroots * 80;
+    for (int j = lane; j < nroots * 16; j += 64) {
+        const int4 v = reinterpret_cast<const int4*>(A3)[j];
+        A2[j] = v.x + v.y + v.z + v.w;
+    }
+    wave_sync();
+    if (lane < nroots * 4) {
+        const int4 v = reinterpret_cast<const int4*>(A2)[lane];
+        A1[lane] = v.x + v.y + v.z + v.w;
+    }
+    if (lane < nroots) s_tag[lane] = (uint16_t)lane;  // root at list position i: gid_0 = i, depth 0
+    wave_sync();
+    int nL = nroots, cur = 0, nseq = nini, npass = 0;
+    bool inner = false;
+    for (int p = 1; p <= 3; ++p) {
+        if (nL > 64) break;
+        const ONode* old = cur ? s_node1 : s_node0;
+        ONode* nw = cur ? s_node0 : s_node1;
+        const uint16_t* tag_old = s_tag + cur * 256;
+        uint16_t* tag_nw = s_tag + (cur ^ 1) * 256;
+        const bool valid = lane < nL;
+        ONode nd{};
+        int tag = 0;
+        if (valid) {
+            nd = old[lane];
+            tag = tag_old[lane];
+        }
+        // (every node with > 1 key was divided by each pass so far: such a node is at depth p - 1)
+        const bool div = valid && nd.cnt > 1;
+        const int gid = tag & 0xFFF;
+        int4 c = make_int4(0, 0, 0, 0);
+        if (div) c = reinterpret_cast<const int4*>(p == 1 ? A1 : (p == 2 ? A2 : A3))[gid];
+        const int nch = (c.x != 0) + (c.y != 0) + (c.z != 0) + (c.w != 0);
+        const int nexp = (c.x > 1) + (c.y > 1) + (c.z > 1) + (c.w > 1);
+        const int v = valid ? (div ? nch << 16 : 1) : 0;
+        const int incl = wave_incl_scan_dpp(v);
+        const int tot = __builtin_amdgcn_readlane(incl, 63);
+        const int C = tot >> 16, S = tot & 0xFFFF, nNew = C + S;
+        const bool bad = nNew > ncap || nseq + C > 0x0FFFFFFF;
+        const bool done = nNew >= N || nNew == nL;
+        if (bad || done) break;
+        const int tot_exp = __popcll(__ballot(nexp >= 1)) + __popcll(__ballot(nexp >= 2)) +
+                            __popcll(__ballot(nexp >= 3)) + __popcll(__ballot(nexp >= 4));
+        if (div) {
+            int pp = (incl - v) >> 16;
+            const int cq[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (cq[q] > 0) {
+                    const int pos = C - 1 - pp;
+                    ONode ch = child_rect(nd, q);
+                    ch.cnt = (uint32_t)cq[q];
+                    ch.seq = (uint32_t)(nseq + pp);
+                    nw[pos] = ch;
+                    tag_nw[pos] = (uint16_t)((gid * 4 + q) | (p << 12));
+                    ++pp;
+                }
+        } else if (valid) {
+            const int pos = C + ((incl - v) & 0xFFFF);
+            nw[pos] = nd;
+            tag_nw[pos] = (uint16_t)tag;
+        }
+        if (lane == 0 && trace && f == 0) {  // the pass record the per-pass code writes (no kstop: a main pass)
+            int* t = trace + l * 512 + 2 + (p - 1) * 8;
+            t[0] = 0; t[1] = nL; t[2] = C; t[3] = S; t[4] = tot_exp; t[5] = -1; t[6] = nk; t[7] = N;
+            trace[l * 512] = p;
+        }
+        wave_sync();
+        nseq += C;
+        cur ^= 1;
+        nL = nNew;
+        npass = p;
+        if (nNew + tot_exp * 3 > N) {  // :678
+            inner = true;
+            break;
+        }
+    }
+    // a node at depth d holds the 4^(3-d) bins below its gid
+    const uint16_t* tag_cur = s_tag + cur * 256;
+    for (int i = lane; i < nL; i += 64) {
+        const int tag = tag_cur[i];
+        const int sh = 2 * (3 - (tag >> 12));
+        const int b0 = (tag & 0xFFF) << sh;
+        for (int j = 0; j < (1 << sh); ++j) s_tab[b0 + j] = (uint16_t)i;
+    }
+    if (lane == 0) {
+        s_misc[27] = nL;
+        s_misc[28] = cur;
+        s_misc[29] = nseq;
+        s_misc[30] = inner;
+        s_misc[31] = npass;
+        if (trace && f == 0) trace[l * 512 + 1] = 1 + npass;  // (0: the level took the per-pass path)
+    }
+}
+
 template <int NT, bool LDS>
 __device__ void octree_body(const Geom& g, const LevelGeom& L, int l, int f, int nk, int ncells, int ncap, int ncap2,
                             const uint32_t* __restrict__ cand, uint32_t* __restrict__ out,
                             int* __restrict__ oct_count, int* __restrict__ err, int* __restrict__ trace,
                             KeyStore<LDS> ks, QuadCounts<LDS> qc, int* s_misc, ONode* s_node0, ONode* s_node1,
-                            int* s_aux0, int* s_aux1, uint8_t* s_flag, int* s_cellofs) {
+                            int* s_aux0, int* s_aux1, uint8_t* s_flag, int* s_cellofs, uint8_t* s_fused, bool fused) {
     const int tid = threadIdx.x;
     int* s_tmp = s_misc;
 
@@ -406,11 +572,36 @@ __device__ void octree_body(const Geom& g, const LevelGeom& L, int l, int f, int
     OCT_T(2);
     // 3. passes.  The pass state (list size, buffer, phase, next seq) is kept
     // in registers: every thread derives it from the same block-scan totals.
-    int nL = nroots, cur = 0, nseq = nini;
+    int nL = nroots, cur = 0, nseq = nini, guard0 = 0;
     bool inner = false;
+    // (nroots is block-uniform; read as a scalar so the branch is a scalar compare)
+    const int nroots_u = __builtin_amdgcn_readfirstlane(nroots);
+    if (fused && nroots_u >= 1 && nroots_u <= kFusedRoots) {
+        // 3a. the first (up to) three main passes from one sweep over the keys
+        int* s_bins = reinterpret_cast<int*>(s_fused);
+        const uint16_t* s_tab = reinterpret_cast<const uint16_t*>(s_fused + kFusedTabOfs);
+        for (int i = tid; i < nroots * 84; i += NT) s_bins[i] = 0;
+        __syncthreads();
+        fused_sweep<NT>(ks, s_node0, s_bins, nk);
+        __syncthreads();
+        OCT_T(56);
+        if (tid < 64) wave_replay(s_node0, s_node1, s_fused, s_misc, nroots, nini, N, ncap, nk, l, f, trace, tid);
+        __syncthreads();
+        OCT_T(57);
+        nL = s_misc[27];
+        cur = s_misc[28];
+        nseq = s_misc[29];
+        inner = s_misc[30] != 0;
+        guard0 = s_misc[31];
+        for (int k = tid; k < nk; k += NT) ks.set_node(k, (int)s_tab[ks.node(k)]);
+        __syncthreads();
+        OCT_T(58);
+    } else if (tid == 0 && trace && f == 0) {
+        trace[l * 512 + 1] = 0;  // (the level took the per-pass path)
+    }
     uint32_t* s_best = reinterpret_cast<uint32_t*>(s_aux0);  // (step 4's words, in aux0)
     int best_state = 0;  // 1: zeroed by the last pass, 2: filled by its remap
-    for (int guard = 0; guard < 4096; ++guard) {
+    for (int guard = guard0; guard < 4096; ++guard) {
         ONode* old = cur ? s_node1 : s_node0;
         ONode* nw = cur ? s_node0 : s_node1;
         // the inner pass's sort keys live in the next list's buffer: it is
@@ -695,7 +886,7 @@ __global__ __launch_bounds__(NT) void octree_kernel(Geom g, const uint32_t* __re
                                                           uint32_t* __restrict__ oct_out,
                                                           int* __restrict__ oct_count, int* __restrict__ err,
                                                           int* __restrict__ trace, OctreeGroup A, OctreeGroup B,
-                                                          int batch) {
+                                                          int batch, int fused) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     // linear block index: group A's (frame, level) blocks first, then group B's, so B's
     // short workgroups fill the slots of A's finished ones inside one launch
@@ -723,7 +914,9 @@ __global__ __launch_bounds__(NT) void octree_kernel(Geom g, const uint32_t* __re
     const size_t o_aux0 = o_qc + (size_t)ncap * 8;
     const size_t o_aux1 = o_aux0 + (size_t)ncap * 4;
     const size_t o_flag = o_aux1 + (size_t)ncap * 4;
-    const size_t o_keys = o_flag + (size_t)ncap;
+    // (the fused sweep's counters, table and tags lie over qc .. flag, all idle
+    // between the roots phase and the first per-pass pass)
+    const size_t o_keys = o_qc + std::max((size_t)ncap * 17, (size_t)kFusedBytes);
     const size_t o_knode = o_keys + (size_t)kcap * 4;
     int* s_misc = reinterpret_cast<int*>(smem);
     ONode* s_node0 = reinterpret_cast<ONode*>(smem + o_node0);
@@ -745,13 +938,13 @@ __global__ __launch_bounds__(NT) void octree_kernel(Geom g, const uint32_t* __re
         KeyStore<true> ks{reinterpret_cast<uint32_t*>(smem + o_keys), reinterpret_cast<uint16_t*>(smem + o_knode)};
         QuadCounts<true> qc{reinterpret_cast<uint16_t*>(smem + o_qc)};
         octree_body<NT, true>(g, L, l, f, nk, ncells, ncap, ncap2, cand, out, oct_count, err, trace, ks, qc, s_misc,
-                              s_node0, s_node1, s_aux0, s_aux1, s_flag, s_cellofs);
+                              s_node0, s_node1, s_aux0, s_aux1, s_flag, s_cellofs, smem + o_qc, fused != 0);
     } else {  // too many candidates for LDS: the same algorithm on an HBM scratch region
         KeyStore<false> ks{gkeys + (size_t)f * g.cand_frame + L.cand_offset,
                            gknode + (size_t)f * g.cand_frame + L.cand_offset};
         QuadCounts<false> qc{reinterpret_cast<uint32_t*>(smem + o_keys)};
         octree_body<NT, false>(g, L, l, f, nk, ncells, ncap, ncap2, cand, out, oct_count, err, trace, ks, qc, s_misc,
-                               s_node0, s_node1, s_aux0, s_aux1, s_flag, s_cellofs);
+                               s_node0, s_node1, s_aux0, s_aux1, s_flag, s_cellofs, smem + o_qc, fused != 0);
     }
 }
 
@@ -759,18 +952,18 @@ __global__ __launch_bounds__(NT) void octree_kernel(Geom g, const uint32_t* __re
 
 size_t octree_lds_bytes(const Geom& g, int kcap, int ncap) {
     // misc, node 0, node 1 (or the cell offsets), u16 quadrant counters,
-    // aux0, aux1, flags, keys + key nodes (or u32 quadrant counters); ncap
+    // aux0, aux1, flags (or the fused sweep's scratch), keys + key nodes (or u32 quadrant counters); ncap
     // is a multiple of 16 and kcap of 64 (see the kernel's carve)
     auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t n = (size_t)ncap;
     return r16(32 * 4) + r16(n * 16) + std::max(r16(n * 16), r16((size_t)(g.max_cells_level + 1) * 4)) +
-           r16(n * 8) + 2 * r16(n * 4) + r16(n) +
+           std::max(r16(n * 8) + 2 * r16(n * 4) + r16(n), (size_t)kFusedBytes) +
            std::max(r16((size_t)kcap * 4) + r16((size_t)kcap * 2), r16(n * 16));
 }
 
 hipError_t launch_octree(const Geom& g, int batch, const uint32_t* cand, const int* cell_counts,
                          uint32_t* gkeys, uint16_t* gknode, uint32_t* oct_out, int* oct_count,
-                         int* err, const OctreeGroup* groups, int ngroups, int* trace, hipStream_t stream) {
+                         int* err, const OctreeGroup* groups, int ngroups, int* trace, bool fused, hipStream_t stream) {
     // both level groups in one launch, LDS sized for the larger group: group B's short
     // workgroups start as group A's finish instead of after the last of them (two
     // launches: 0.278 ms per 512 frames, one: 0.184 ms)
@@ -784,7 +977,7 @@ hipError_t launch_octree(const Geom& g, int batch, const uint32_t* cand, const i
                                     octree_lds_bytes(g, groups[1].kcap, groups[1].ncap));
         hipLaunchKernelGGL(kernel, dim3((groups[0].nlev + groups[1].nlev) * batch), dim3(nt), lds,
                            stream, g, cand, cell_counts, gkeys, gknode, oct_out, oct_count, err, trace, groups[0],
-                           groups[1], batch);
+                           groups[1], batch, fused ? 1 : 0);
         return hipGetLastError();
     }
     // one launch per level group: the LDS (and so the workgroups per CU) sized for the group's levels
@@ -793,7 +986,7 @@ hipError_t launch_octree(const Geom& g, int batch, const uint32_t* cand, const i
         if (G.nlev <= 0) continue;
         const size_t lds = octree_lds_bytes(g, G.kcap, G.ncap);
         hipLaunchKernelGGL(kernel, dim3(G.nlev * batch), dim3(nt), lds, stream, g, cand, cell_counts,
-                           gkeys, gknode, oct_out, oct_count, err, trace, G, OctreeGroup{0, 0, 0, 0}, batch);
+                           gkeys, gknode, oct_out, oct_count, err, trace, G, OctreeGroup{0, 0, 0, 0}, batch, fused ? 1 : 0);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -133,6 +133,7 @@ def lib() -> ctypes.CDLL:
         L.orbgpu_debug_level_octree.argtypes = [vp, i, i, vp, i]
         L.orbgpu_debug_octree_trace.argtypes = [vp, i, vp, i]
         L.orbgpu_debug_pyramid_emulate.argtypes = [i, f, i, i, i, vp, sz, vp, sz, vp]
+        L.orbgpu_debug_octree_plan.argtypes = [i, f, i, i, i, vp]
         L.orbgpu_search_for_initialization.argtypes = [GridBounds, vp, vp, i, vp, vp, i, vp, i, f, i, vp,
                                                        ctypes.POINTER(i)]
         # orbgpu_frame.h
@@ -254,6 +255,16 @@ def pyramid_plan_emulate(img: np.ndarray, nfeatures=1000, scale_factor=1.2, nlev
     keys = ("ticks", "rows_per_chunk", "compute_waves", "producer_waves", "loads_per_lane", "entries_per_lane",
             "lds_bytes", "ring0_rows")
     return levels, dict(zip(keys, (int(v) for v in info)))
+
+
+def octree_plan(nfeatures=1000, scale_factor=1.2, nlevels=8, width=640, height=480):
+    """The octree launch's two level groups (orbgpu_debug_octree_plan): first
+    level, levels, keys and nodes held in LDS, LDS bytes per workgroup.  Needs no GPU."""
+    out = np.zeros(10, np.int32)
+    _check(lib().orbgpu_debug_octree_plan(nfeatures, scale_factor, nlevels, width, height, out.ctypes.data),
+           "orbgpu_debug_octree_plan")
+    keys = ("level0", "levels", "kcap", "ncap", "lds_bytes")
+    return [dict(zip(keys, (int(v) for v in out[5 * g:5 * g + 5]))) for g in range(2)]
 
 
 def _ptr(a) -> int:
