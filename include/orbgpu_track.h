@@ -23,12 +23,15 @@
  * reads its pose from HBM.  A frame that is not in a stage hands that stage an
  * empty job (n = 0) or an idle call.
  *
- * UpdateLocalMap (Tracking.cpp:1217) sits between the two halves; it is map
- * bookkeeping on the host and depends on the first half's matches, so the
- * chain is two entry points.  The MapPoint counters (IncreaseVisible,
- * IncreaseFound), mbTrackInView / mnLastFrameSeen and the fallback from the
- * motion model to the reference keyframe stay with the caller, who re-submits
- * a FEW_MATCHES or LOST frame in reference mode as Track() does.
+ * UpdateLocalMap (Tracking.cpp:1217) sits between the two halves and depends on
+ * the first half's matches, so the chain is two entry points here.  The caller
+ * either runs it on the host, or calls orbgpu_update_local_map_batch_device
+ * (orbgpu_localmap.h) between the two on the same stream: it reads call 1's
+ * rows in place and writes call 2's table, frame_mp and job.  The MapPoint
+ * counters (IncreaseVisible, IncreaseFound), mbTrackInView / mnLastFrameSeen
+ * and the fallback from the motion model to the reference keyframe stay with
+ * the caller, who re-submits a FEW_MATCHES or LOST frame in reference mode as
+ * Track() does.
  *
  * Quirks of the reference that are kept:
  *   - the 2*th retry starts from an all-NULL mvpMapPoints (:1158), so a match

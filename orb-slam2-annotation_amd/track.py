@@ -9,7 +9,13 @@ include/orbgpu_track.h (csrc/track.hip).
   ``initial`` (TrackWithMotionModel / TrackReferenceKeyFrame,
   src/Tracking.cpp:1126-1198, :977-1025) and ``local_map`` (SearchLocalPoints +
   TrackLocalMap, :1496-1562, :1210-1264).  UpdateLocalMap, between the two, is
-  the caller's; ``local_map`` can read the pose ``initial`` left in place.
+  either the caller's (``local_map`` takes a host-built table and can read the
+  pose ``initial`` left in place) or ``update_local_map`` (:1571-1745,
+  include/orbgpu_localmap.h, csrc/localmap.hip), which reads ``initial``'s rows
+  in place and a ``MapMirror`` and fills the buffers ``prepare_local_map``
+  allocated: ``run_initial; run_update_local_map; run_local_map`` is then three
+  launches on one stream and no upload.
+* ``MapMirror`` -- the map's keyframes and points as plain arrays in HBM.
 * ``update_last_frame`` -- UpdateLastFrame's visual-odometry points
   (:1053-1113) for stereo / RGB-D streams.
 
@@ -76,6 +82,31 @@ class UpdateLastFrameResult(ctypes.Structure):
                 ("n_visited", ctypes.c_int)]
 
 
+LM_OK, LM_KEPT, LM_CAPACITY, LM_BAD_JOB = range(4)  # ORBGPU_LOCALMAP_*
+
+
+class MapMirrorStruct(ctypes.Structure):
+    _fields_ = [("n_kf", ctypes.c_int), ("n_pt", ctypes.c_int), ("n_slots_total", ctypes.c_int),
+                ("n_children_total", ctypes.c_int), ("n_obs_total", ctypes.c_int), ("pad", ctypes.c_int),
+                ("kf_bad", vp), ("slot_offset", vp), ("n_slots", vp), ("slots", vp), ("covis", vp),
+                ("child_offset", vp), ("n_children", vp), ("children", vp), ("parent", vp), ("kf_by_rank", vp),
+                ("pt_flags", vp), ("obs_offset", vp), ("n_obs", vp), ("obs", vp), ("pos", vp), ("normal", vp),
+                ("desc", vp), ("min_dist", vp), ("max_dist", vp)]
+
+
+class UpdateLocalMapJob(ctypes.Structure):
+    _fields_ = [("n_kp", ctypes.c_int), ("src_n", ctypes.c_int), ("n_prev_kfs", ctypes.c_int), ("pad", ctypes.c_int),
+                ("rows", vp), ("src_pt_id", vp), ("src_pos", vp), ("src_desc", vp), ("prev_kfs", vp),
+                ("out_flags", vp), ("out_pos", vp), ("out_normal", vp), ("out_desc", vp), ("out_min_dist", vp),
+                ("out_max_dist", vp), ("frame_mp", vp), ("local_job", vp)]
+
+
+class UpdateLocalMapResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int), ("n_k1", ctypes.c_int), ("n_local_kfs", ctypes.c_int),
+                ("ref_kf", ctypes.c_int), ("n_nulled", ctypes.c_int), ("n_local", ctypes.c_int),
+                ("n_extra", ctypes.c_int), ("pad", ctypes.c_int)]
+
+
 def _lib():
     global _BOUND
     L = orbgpu.lib()
@@ -88,6 +119,10 @@ def _lib():
         L.orbgpu_track_local_workspace_bytes.restype = ctypes.c_size_t
         L.orbgpu_track_local_map_batch_device.argtypes = [i, vp, i, vp, i, i, vp, vp, vp, vp, vp]
         L.orbgpu_update_last_frame_batch_device.argtypes = [i, vp, i, vp, vp, vp]
+        L.orbgpu_update_local_map_workspace_bytes.argtypes = [i, i, i, i, i, i]
+        L.orbgpu_update_local_map_workspace_bytes.restype = ctypes.c_size_t
+        L.orbgpu_update_local_map_batch_device.argtypes = [i, vp, ctypes.POINTER(MapMirrorStruct), i, i, i, vp, vp, vp,
+                                                           vp, vp]
         _BOUND = True
     return L
 
@@ -124,6 +159,44 @@ class PointTable:
         for name, _ in self.FIELDS:
             setattr(P, name, _ptr(self.t.get(name)))
         return P
+
+
+def _ragged(lists):
+    """per-row offsets, counts and the concatenation of a list of int lists"""
+    cnt = np.array([len(x) for x in lists], np.int32)
+    off = (np.cumsum(cnt) - cnt).astype(np.int32)
+    flat = np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in lists] + [np.zeros(0, np.int32)])
+    return off, cnt, flat.astype(np.int32)
+
+
+class MapMirror:
+    """The map as Tracking::UpdateLocalMap reads it, uploaded from numpy (include/orbgpu_localmap.h): kf_bad
+    (n_kf,), slots (per keyframe an int array of point ids, -1 = NULL), covis (n_kf, 10) -1 padded, children
+    (per keyframe a list, in the order that stands for the std::set's), parent (n_kf,), kf_by_rank (None or a
+    permutation: the order that stands for the std::map's); pt_flags (n_pt,) of proj.VALID / proj.HAS_OBS, obs
+    (per point a list of keyframes), pos, normal (n_pt, 3), desc (n_pt, 32), min_dist, max_dist (n_pt,).  The
+    caller keeps it current; many jobs and calls share one."""
+
+    def __init__(self, kf_bad, slots, covis, children, parent, pt_flags, obs, pos, normal, desc, min_dist, max_dist,
+                 kf_by_rank=None, device="cuda"):
+        so, sn, sf = _ragged(slots)
+        co, cn, cf = _ragged(children)
+        oo, on, of = _ragged(obs)
+        host = {"kf_bad": (kf_bad, np.uint8), "slot_offset": (so, np.int32), "n_slots": (sn, np.int32),
+                "slots": (sf, np.int32), "covis": (covis, np.int32), "child_offset": (co, np.int32),
+                "n_children": (cn, np.int32), "children": (cf, np.int32), "parent": (parent, np.int32),
+                "pt_flags": (pt_flags, np.int32), "obs_offset": (oo, np.int32), "n_obs": (on, np.int32),
+                "obs": (of, np.int32), "pos": (pos, np.float32), "normal": (normal, np.float32),
+                "desc": (desc, np.uint8), "min_dist": (min_dist, np.float32), "max_dist": (max_dist, np.float32)}
+        if kf_by_rank is not None:
+            host["kf_by_rank"] = (kf_by_rank, np.int32)
+        self.t = {name: _up(a, dt, device) for name, (a, dt) in host.items()}
+        self.n_kf, self.n_pt = len(kf_bad), len(pt_flags)
+        c = self.c = MapMirrorStruct()
+        c.n_kf, c.n_pt = self.n_kf, self.n_pt
+        c.n_slots_total, c.n_children_total, c.n_obs_total = len(sf), len(cf), len(of)
+        for name, t in self.t.items():
+            setattr(c, name, _ptr(t))
 
 
 def _pose16(T):
@@ -258,6 +331,125 @@ class TrackStep:
     def point_flags(self):
         """(n, point_stride) uint8 of PT_SEEN / PT_IN_VIEW per table entry"""
         return self.d_point_flags[:self.n_local].cpu().numpy()
+
+
+    # ---- 1b. UpdateLocalMap: call 2's table, frame_mp and job made on the device --------
+    TABLE = (("flags", np.int32, ()), ("pos", np.float32, (3,)), ("normal", np.float32, (3,)), ("desc", np.uint8, (32,)),
+             ("min_dist", np.float32, ()), ("max_dist", np.float32, ()))
+
+    def prepare_local_map(self, jobs, point_stride, n_frames=None):
+        """Allocates, once, everything call 2 reads and writes for len(jobs) frames: per frame a table of
+        point_stride entries and a frame_mp row that update_local_map fills, the jobs (dicts with frame, Tcw --
+        16 or 12 floats or a device address such as initial_pose_ptr(k) -- th and optionally stereo,
+        only_tracking, recently_relocalised; n_local, points and frame_mp are the device's to write), the
+        workspace, the results, the rows and the point flags.  Nothing is launched."""
+        import torch
+        n, S, dev, P = len(jobs), self.stride, self.device, int(point_stride)
+        N = max(n, 1)
+        tt = {"flags": torch.int32, "desc": torch.uint8}
+        self.d_table = {name: torch.zeros((N, P) + shape, dtype=tt.get(name, torch.float32), device=dev)
+                        for name, _, shape in self.TABLE}
+        self.d_frame_mp = torch.zeros((N, S), dtype=torch.int32, device=dev)
+        tab = (TrackLocalJob * N)()
+        held = []
+        for J, j in zip(tab, jobs):
+            J.frame = int(j["frame"])
+            J.stereo, J.only_tracking = int(j.get("stereo", 0)), int(j.get("only_tracking", 0))
+            J.recently_relocalised = int(j.get("recently_relocalised", 0))
+            J.th = float(j.get("th", 1.0))
+            T = j["Tcw"]
+            if isinstance(T, int):
+                J.Tcw = T
+            elif T is not None:
+                t = _up(_pose16(T), np.float32, dev)
+                held.append(t)
+                J.Tcw = t.data_ptr()
+        L = _lib()
+        self.n_local, self.point_stride = n, P
+        self.d_local_jobs = bow.to_device_table(tab, dev)
+        self.local_ws = torch.zeros(L.orbgpu_track_local_workspace_bytes(N, S, P), dtype=torch.uint8, device=dev)
+        self.d_local_results = torch.zeros(N * ctypes.sizeof(TrackLocalResult), dtype=torch.uint8, device=dev)
+        self.d_local_rows = torch.zeros((N, LOCAL_ROWS, S), dtype=torch.int32, device=dev)
+        self.d_point_flags = torch.zeros((N, P), dtype=torch.uint8, device=dev)
+        self._held_local = held
+        self._n_frames_local = self.frames.n_f if n_frames is None else n_frames
+
+    def update_local_map(self, jobs, mirror, stream=None, kf_stride=128, launch=True):
+        """Tracking::UpdateLocalMap for the frames of prepare_local_map, one job each: dicts with n_kp,
+        src_pt_id ((src_n,) int32: per entry of call 1's table the mirror's point id or -1), table (call 1's
+        PointTable, read for the -1 entries' pos and desc; or None), prev_kfs (mvpLocalKeyFrames before the
+        call) and optionally rows ((2, stride) int32, uploaded; default: job k reads initial's rows of job k in
+        place).  Fills the tables, frame_mp and jobs that run_local_map then reads."""
+        import torch
+        n, S, dev, P, KS = len(jobs), self.stride, self.device, self.point_stride, int(kf_stride)
+        assert n == self.n_local, "prepare_local_map() first, for as many frames"
+        N = max(n, 1)
+        tab = (UpdateLocalMapJob * N)()
+        held = [mirror]
+        sz = ctypes.sizeof(TrackLocalJob)
+        for k, (J, j) in enumerate(zip(tab, jobs)):
+            src = _up(j["src_pt_id"], np.int32, dev)
+            prev = _up(j.get("prev_kfs", []), np.int32, dev)
+            J.n_kp, J.src_n, J.n_prev_kfs = int(j["n_kp"]), int(j.get("src_n", src.numel() // 4)), prev.numel() // 4
+            rows = j.get("rows")
+            if rows is not None:
+                r = np.full((2, S), -1, np.int32)
+                rows = np.asarray(rows, np.int32)
+                r[:, :min(rows.shape[1], S)] = rows[:, :S]
+                rows = _up(r, np.int32, dev)
+                J.rows = rows.data_ptr()
+            else:
+                J.rows = self.d_initial_rows.data_ptr() + k * INITIAL_ROWS * S * 4
+            J.src_pt_id, J.prev_kfs = _ptr(src), _ptr(prev)
+            t = j.get("table")
+            if t is not None:
+                J.src_pos, J.src_desc = _ptr(t.t.get("pos")), _ptr(t.t.get("desc"))
+            for name, _, _ in self.TABLE:
+                d = self.d_table[name]
+                setattr(J, "out_" + name, d.data_ptr() + k * d.stride(0) * d.element_size())
+            J.frame_mp = self.d_frame_mp.data_ptr() + k * S * 4
+            J.local_job = self.d_local_jobs.data_ptr() + k * sz
+            held += [src, prev, rows, t]
+        L = _lib()
+        self.mirror, self.kf_stride = mirror, KS
+        self.d_lm_jobs = bow.to_device_table(tab, dev)
+        self.lm_ws = torch.empty(L.orbgpu_update_local_map_workspace_bytes(N, S, P, KS, mirror.n_kf, mirror.n_pt),
+                                 dtype=torch.uint8, device=dev)
+        self.d_lm_results = torch.zeros(N * ctypes.sizeof(UpdateLocalMapResult), dtype=torch.uint8, device=dev)
+        self.d_local_kfs = torch.zeros((N, KS), dtype=torch.int32, device=dev)
+        self.d_local_points = torch.zeros((N, P), dtype=torch.int32, device=dev)
+        self._held_lm = held
+        if launch:
+            self.run_update_local_map(stream)
+
+    def run_update_local_map(self, stream=None):
+        """the call for the jobs `update_local_map` uploaded last, again (no allocation, no upload)"""
+        orbgpu._check(_lib().orbgpu_update_local_map_batch_device(
+            self.n_local, self.d_lm_jobs.data_ptr(), ctypes.byref(self.mirror.c), self.stride, self.point_stride,
+            self.kf_stride, self.lm_ws.data_ptr(), self.d_lm_results.data_ptr(), self.d_local_kfs.data_ptr(),
+            self.d_local_points.data_ptr(), orbgpu._stream_ptr(stream)), "orbgpu_update_local_map_batch_device")
+
+    def update_results(self):
+        return loop._struct_rows(self.d_lm_results, UpdateLocalMapResult, self.n_local)
+
+    def local_kfs(self):
+        """(n, kf_stride) int32: mvpLocalKeyFrames; the first n_local_kfs of a row are written"""
+        return self.d_local_kfs[:self.n_local].cpu().numpy()
+
+    def local_points(self):
+        """(n, point_stride) int32: the mirror ids of mvpLocalMapPoints; the first n_local of a row are written"""
+        return self.d_local_points[:self.n_local].cpu().numpy()
+
+    def prepared_tables(self):
+        """call 2's tables as the device filled them: name -> (n, point_stride, ..) numpy"""
+        return {name: t[:self.n_local].cpu().numpy() for name, t in self.d_table.items()}
+
+    def prepared_frame_mp(self):
+        return self.d_frame_mp[:self.n_local].cpu().numpy()
+
+    def prepared_jobs(self):
+        """call 2's jobs as they stand on the device"""
+        return loop._struct_rows(self.d_local_jobs, TrackLocalJob, self.n_local)
 
 
 def update_last_frame(frames, stride=None, device="cuda", stream=None):
