@@ -10,6 +10,10 @@ include/orbgpu_localba.h (Optimizer::LocalBundleAdjustment, src/Optimizer.cpp:
   Xw, erase, result).
 * ``make_jobs`` / ``make_batch`` -- job records, and the concatenated arrays of
   a list of problems.
+* ``MapMirrorBA`` / ``MapLocalBA`` -- against a ``track.MapMirror``
+  (include/orbgpu_localba_map.h, csrc/localba_map.hip): the gather of the
+  arrays from the map, the solve above and the collection of vToErase with the
+  write-back into the mirror, three calls on one stream.
 """
 from __future__ import annotations
 
@@ -160,3 +164,151 @@ def local_bundle_adjustment(Tcw, fixed, cam, Xw, pose_idx, point_idx, obs, inv_s
                                inv_sigma2=inv_sigma2, n_local=n_local)])
     res, T, X, er = local_ba_batch(jobs, *(a[n] for n, *_ in INPUTS))
     return T.reshape(-1, 4, 4).copy(), X, er.astype(bool), res[0]
+
+
+# ---- against the map mirror: gather, solve, collect on one stream (include/orbgpu_localba_map.h) ----
+
+MAP_OK, MAP_CAPACITY, MAP_BAD_JOB = 0, 2, 3  # ORBGPU_LOCALBA_MAP_*
+_vp = ctypes.c_void_p
+_MAP_BOUND = False
+
+
+class MapMirrorBAStruct(ctypes.Structure):
+    _fields_ = [("n_covis_all_total", ctypes.c_int), ("pad", ctypes.c_int), ("covis_all_offset", _vp),
+                ("n_covis_all", _vp), ("covis_all", _vp), ("kf_first", _vp), ("kf_Tcw", _vp), ("kf_cam", _vp),
+                ("kp_obs", _vp), ("kp_inv_sigma2", _vp), ("obs_idx", _vp)]
+
+
+class GatherJob(ctypes.Structure):
+    _fields_ = [("kf", ctypes.c_int), ("pad", ctypes.c_int)]
+
+
+class GatherResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int), ("n_local", ctypes.c_int), ("n_fixed", ctypes.c_int),
+                ("n_points", ctypes.c_int), ("n_edges", ctypes.c_int), ("n_mono", ctypes.c_int),
+                ("n_stereo", ctypes.c_int), ("pad", ctypes.c_int)]
+
+
+GATHER_RESULT_DTYPE = np.dtype([(name, "<i4") for name, _ in GatherResult._fields_])
+assert GATHER_RESULT_DTYPE.itemsize == ctypes.sizeof(GatherResult) == 32 and ctypes.sizeof(GatherJob) == 8
+
+# the lists a write-back needs: (name, which stride counts its entries per job)
+LISTS = (("local_kfs", "kf"), ("fixed_kfs", "pose"), ("local_points", "point"), ("edge_kf", "edge"), ("edge_slot", "edge"))
+
+
+def _map_lib():
+    global _MAP_BOUND
+    L = orbgpu.lib()
+    if not _MAP_BOUND:
+        import track
+        i = ctypes.c_int
+        L.orbgpu_local_ba_gather_workspace_bytes.argtypes = [i, i, i]
+        L.orbgpu_local_ba_gather_workspace_bytes.restype = ctypes.c_size_t
+        L.orbgpu_local_ba_gather_batch_device.argtypes = [i, _vp, ctypes.POINTER(track.MapMirrorStruct),
+                                                           ctypes.POINTER(MapMirrorBAStruct), i, i, i, i] + [_vp] * 17
+        L.orbgpu_local_ba_collect_batch_device.argtypes = [i, _vp, i, i, i] + [_vp] * 11 + [i, i, _vp, _vp, _vp]
+        _MAP_BOUND = True
+    return L
+
+
+class MapMirrorBA:
+    """What the gather reads beside a track.MapMirror, uploaded from numpy: covis_all (per keyframe the whole
+    ordered covisibility list), kf_first (n_kf,), kf_Tcw (n_kf, 12), kf_cam (n_kf, 5), kp_obs / kp_inv_sigma2
+    (per keyframe an (n_slots, 3) / (n_slots,) array, parallel to the mirror's slots), obs_idx (per point a
+    list parallel to its observations).  The caller keeps it current."""
+
+    def __init__(self, covis_all, kf_first, kf_Tcw, kf_cam, kp_obs, kp_inv_sigma2, obs_idx, device="cuda"):
+        import track
+        co, cn, cf = track._ragged(covis_all)
+        flat = lambda rows, cols: np.concatenate([np.asarray(r, np.float32).reshape(-1, cols) for r in rows] +
+                                                 [np.zeros((0, cols), np.float32)])
+        host = {"covis_all_offset": (co, np.int32), "n_covis_all": (cn, np.int32), "covis_all": (cf, np.int32),
+                "kf_first": (kf_first, np.uint8), "kf_Tcw": (kf_Tcw, np.float32), "kf_cam": (kf_cam, np.float32),
+                "kp_obs": (flat(kp_obs, 3), np.float32), "kp_inv_sigma2": (flat(kp_inv_sigma2, 1), np.float32),
+                "obs_idx": (track._ragged(obs_idx)[2], np.int32)}
+        self.t = {name: track._up(a, dt, device) for name, (a, dt) in host.items()}
+        c = self.c = MapMirrorBAStruct()
+        c.n_covis_all_total = len(cf)
+        for name, t in self.t.items():
+            setattr(c, name, track._ptr(t))
+
+
+def gather_workspace_bytes(n: int, n_kf: int, n_pt: int) -> int:
+    return int(_map_lib().orbgpu_local_ba_gather_workspace_bytes(n, n_kf, n_pt))
+
+
+class MapLocalBA:
+    """LocalBundleAdjustment of n keyframes against a track.MapMirror and a MapMirrorBA as three calls on one
+    stream: gather(), solve() (orbgpu_local_ba_batch_device, unchanged) and collect().  Job k owns the rows
+    [k * stride, (k + 1) * stride) of every buffer in `t` (torch tensors), so nothing is downloaded between
+    the calls.  kfs: pKF's index per job."""
+
+    def __init__(self, mirror, mirror_ba, kfs, kf_stride, pose_stride, point_stride, edge_stride, device="cuda"):
+        import torch
+        self.mirror, self.mirror_ba, self.n = mirror, mirror_ba, len(kfs)
+        self.strides = dict(kf=int(kf_stride), pose=int(pose_stride), point=int(point_stride), edge=int(edge_stride))
+        n, S = max(self.n, 1), self.strides
+        jobs = np.zeros((n, 2), np.int32)
+        jobs[:self.n, 0] = np.asarray(kfs, np.int32).reshape(-1)
+        t = self.t = {"gather_jobs": torch.from_numpy(jobs).to(device)}
+        zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)
+        tdt = {np.float32: torch.float32, np.uint8: torch.uint8, np.int32: torch.int32}
+        for name, dtype, cols, total in INPUTS + OUTPUTS:
+            rows = n * S[{"poses": "pose", "local": "kf", "points": "point", "edges": "edge"}[total]]
+            t[name] = zeros((rows, cols) if cols else (rows,), tdt[dtype])
+        for name, stride in LISTS:
+            t[name] = zeros((n, S[stride]), torch.int32)
+        t["to_erase"] = zeros((n, S["edge"], 3), torch.int32)
+        t["n_erase"] = zeros((n,), torch.int32)
+        t["gather_results"] = zeros((n, 32), torch.uint8)
+        t["jobs"] = zeros((n, 32), torch.uint8)
+        t["results"] = zeros((n, 32), torch.uint8)
+        t["gather_ws"] = zeros((max(gather_workspace_bytes(n, mirror.n_kf, mirror.n_pt), 1),), torch.uint8)
+        self._zeros = zeros
+
+    def gather(self, stream=None) -> None:
+        t, S, p = self.t, self.strides, orbgpu._ptr
+        orbgpu._check(_map_lib().orbgpu_local_ba_gather_batch_device(
+            self.n, p(t["gather_jobs"]), ctypes.byref(self.mirror.c), ctypes.byref(self.mirror_ba.c), S["kf"], S["pose"],
+            S["point"], S["edge"], p(t["gather_ws"]), p(t["gather_results"]), p(t["jobs"]),
+            *(p(t[name]) for name, *_ in INPUTS), *(p(t[name]) for name, _ in LISTS), orbgpu._stream_ptr(stream)),
+            "orbgpu_local_ba_gather_batch_device")
+
+    def solve_workspace(self):
+        """LBA's workspace, allocated at its first use: it grows with the square of kf_stride"""
+        import torch
+        if "ws" not in self.t:
+            n, S = max(self.n, 1), self.strides
+            size = workspace_bytes(n, n * S["pose"], n * S["point"], n * S["edge"], S["kf"])
+            self.t["ws"] = self._zeros((max(size, 8),), torch.uint8)
+        return self.t["ws"]
+
+    def solve(self, stream=None) -> None:
+        """call solve_workspace() first when `stream` is not the current one: the allocation is on the current"""
+        t = self.t
+        self.solve_workspace()
+        local_ba_batch_device(t["jobs"][:self.n], *(t[name] for name, *_ in INPUTS), *(t[name] for name, *_ in OUTPUTS),
+                              t["results"][:self.n], t["ws"], self.strides["kf"], stream)
+
+    def collect(self, stream=None, write_mirror=False) -> None:
+        """write_mirror: scatter the optimised poses and points into mirror_ba's kf_Tcw and the mirror's pos
+        (not for a batch whose jobs share a local keyframe or point)"""
+        t, S, p = self.t, self.strides, orbgpu._ptr
+        kf_Tcw = p(self.mirror_ba.t["kf_Tcw"]) if write_mirror else None
+        pos = p(self.mirror.t["pos"]) if write_mirror else None
+        orbgpu._check(_map_lib().orbgpu_local_ba_collect_batch_device(
+            self.n, p(t["jobs"]), S["kf"], S["point"], S["edge"], p(t["obs"]), p(t["edge_point"]), p(t["local_kfs"]),
+            p(t["local_points"]), p(t["edge_kf"]), p(t["edge_slot"]), p(t["erase"]), p(t["Tcw_out"]), p(t["Xw_out"]),
+            p(t["to_erase"]), p(t["n_erase"]), self.mirror.n_kf, self.mirror.n_pt, kf_Tcw, pos,
+            orbgpu._stream_ptr(stream)), "orbgpu_local_ba_collect_batch_device")
+
+    def run(self, stream=None, write_mirror=False) -> None:
+        self.gather(stream)
+        self.solve(stream)
+        self.collect(stream, write_mirror)
+
+    def host(self, name) -> np.ndarray:
+        """a buffer downloaded; the three struct tables as record arrays"""
+        a = self.t[name].cpu().numpy()
+        dt = {"gather_results": GATHER_RESULT_DTYPE, "jobs": JOB_DTYPE, "results": RESULT_DTYPE}.get(name)
+        return a.reshape(-1).view(dt) if dt is not None else a
