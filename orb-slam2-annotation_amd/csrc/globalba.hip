@@ -4,7 +4,8 @@
 // projection edges with their Jacobians, the quadratic form, the Schur
 // complement onto the poses, g2o's Levenberg-Marquardt over the whole vector and
 // the active set of initializeOptimization(0) -- as one launch per phase, and a
-// dense blocked Cholesky of the reduced system that runs over all compute units.
+// dense blocked Cholesky of the reduced system that runs over all compute units
+// (chol_blocked.h, shared with essential.hip).
 // tests/globalba_ref.py is the same arithmetic, expression for expression.  The
 // edge arithmetic and se3_exp_times are repeated from localba.hip, as that file
 // repeats poseopt.hip's; Huber, the quaternion algebra, Rodrigues and the pose
@@ -50,6 +51,7 @@
 #include <string>
 
 #include "../../include/orbgpu_globalba.h"
+#include "chol_blocked.h"
 #include "host_common.h"
 #include "host_ctx.h"
 #include "lm_runtime.h"
@@ -59,9 +61,6 @@ namespace {
 namespace lm = orbgpu::lm;
 
 constexpr int kThreads = 256;
-constexpr int kNB = 48;    // panel width of the factorisation: a multiple of 6
-constexpr int kTile = 16;  // the trailing update works on kTile x kTile entries per workgroup
-constexpr int kRows = 64;  // rows per workgroup of the panel solve
 
 // doubles per pose, point and edge in the workspace, and where each field starts (localba.hip's)
 constexpr int P_EST = 0, P_TRIAL = 7, P_H = 14, kPoseD = 41;                                   // q t | q t | H 21, b 6
@@ -600,126 +599,15 @@ __global__ __launch_bounds__(kThreads) void ba_schur(Args A) {
     A.S[n * n + wi] = PD(P_H + 21 + j, pa) - coef;
 }
 
-// ------------------------------------------------------------------ the blocked Cholesky, panel [c0, c0 + w)
+// ------------------------------------------------------------------ the blocked Cholesky: chol_blocked.h
 
-// step 1, one workgroup: the diagonal block, column by column; a pivot that is not positive sets fail
-__global__ __launch_bounds__(64) void ba_chol_diag(Args A, int c0, int w) {
-    __shared__ double D[kNB][kNB + 1];
-    __shared__ double s_r[kNB];
-    if (A.ctl->fail) return;
-    const size_t n = 6 * (size_t)A.ctl->nf;
-    const int i = threadIdx.x;
-    if (i < w)
-        for (int j = 0; j <= i; ++j) D[i][j] = A.S[(size_t)(c0 + i) * n + c0 + j];
-    __syncthreads();
-    for (int j = 0; j < w; ++j) {
-        if (i >= j && i < w) {
-            double r = D[i][j];
-            for (int k = 0; k < j; ++k) r -= D[i][k] * D[j][k];
-            s_r[i] = r;
-        }
-        __syncthreads();
-        const double pivot = s_r[j];
-        if (!(pivot > 0)) {  // every lane read the same word
-            if (i == 0) A.ctl->fail = 1;
-            return;
-        }
-        const double d = __dsqrt_rn(pivot);
-        if (i == j) D[j][j] = d;
-        if (i > j && i < w) D[i][j] = s_r[i] / d;
-        __syncthreads();
-    }
-    if (i < w)
-        for (int j = 0; j <= i; ++j) A.S[(size_t)(c0 + i) * n + c0 + j] = D[i][j];
-}
-
-// step 2, one lane per row below the block (b_schur's row included): its row of the panel
-__global__ __launch_bounds__(kRows) void ba_chol_panel(Args A, int c0, int w) {
-    __shared__ double D[kNB][kNB + 1];
-    __shared__ double Rw[kRows][kNB + 1];
-    if (A.ctl->fail) return;
-    const size_t n = 6 * (size_t)A.ctl->nf;
-    const int t = threadIdx.x;
-    for (int v = t; v < w * w; v += kRows) {
-        const int a = v / w, b = v % w;
-        if (b <= a) D[a][b] = A.S[(size_t)(c0 + a) * n + c0 + b];
-    }
-    const size_t row = (size_t)c0 + w + (size_t)blockIdx.x * kRows + t;
-    const bool live = row <= n;
-    if (live)
-        for (int j = 0; j < w; ++j) Rw[t][j] = A.S[row * n + c0 + j];
-    __syncthreads();
-    if (!live) return;
-    for (int j = 0; j < w; ++j) {
-        double s = Rw[t][j];
-        for (int k = 0; k < j; ++k) s -= Rw[t][k] * D[j][k];
-        s = s / D[j][j];
-        Rw[t][j] = s;
-        A.S[row * n + c0 + j] = s;
-    }
-}
-
-// step 3, the trailing update: entry (i, j), c0 + w <= j <= i <= n, loses sum_k L(i, k) L(j, k) over the
-// panel's columns in ascending k, from panel rows staged in LDS
-__global__ __launch_bounds__(kTile* kTile) void ba_chol_update(Args A, int c0, int w) {
-    __shared__ double Li[kTile][kNB + 1];
-    __shared__ double Lj[kTile][kNB + 1];
-    if (A.ctl->fail) return;
-    if (blockIdx.x > blockIdx.y) return;  // tiles above the diagonal
-    const size_t n = 6 * (size_t)A.ctl->nf;
-    const size_t c1 = (size_t)c0 + w;
-    const int tx = threadIdx.x % kTile, ty = threadIdx.x / kTile;
-    const size_t i0 = c1 + (size_t)blockIdx.y * kTile, j0 = c1 + (size_t)blockIdx.x * kTile;
-    for (int k = tx; k < w; k += kTile) {
-        Li[ty][k] = i0 + ty <= n ? A.S[(i0 + ty) * n + c0 + k] : 0.0;
-        Lj[ty][k] = j0 + ty < n ? A.S[(j0 + ty) * n + c0 + k] : 0.0;
-    }
-    __syncthreads();
-    const size_t i = i0 + ty, j = j0 + tx;
-    if (i > n || j >= n || j > i) return;
-    double s = A.S[i * n + j];
-    for (int k = 0; k < w; ++k) s -= Li[ty][k] * Lj[tx][k];
-    A.S[i * n + j] = s;
-}
-
-// L^T x = y, column oriented, panels descending; y is row n of the matrix and becomes the running s.
-// One workgroup solves the panel's own block ...
-__global__ __launch_bounds__(64) void ba_back_diag(Args A, int c0, int w) {
-    __shared__ double D[kNB][kNB + 1];
-    __shared__ double s_s[kNB];
-    __shared__ double s_x;
-    if (A.ctl->fail) return;
-    const size_t n = 6 * (size_t)A.ctl->nf;
-    const int k = threadIdx.x;
-    if (k < w) {
-        for (int j = 0; j <= k; ++j) D[k][j] = A.S[(size_t)(c0 + k) * n + c0 + j];
-        s_s[k] = A.S[n * n + c0 + k];
-    }
-    __syncthreads();
-    for (int i = w - 1; i >= 0; --i) {
-        if (k == i) {
-            s_x = s_s[i] / D[i][i];
-            A.x[c0 + i] = s_x;
-        }
-        __syncthreads();
-        if (k < i) s_s[k] -= D[i][k] * s_x;
-        __syncthreads();
-    }
-}
-
-// ... then one lane per row above it takes the panel's x out of its s, i descending
-__global__ __launch_bounds__(kThreads) void ba_back_rows(Args A, int c0, int w) {
-    __shared__ double s_x[kNB];
-    if (A.ctl->fail) return;
-    const size_t n = 6 * (size_t)A.ctl->nf;
-    if ((int)threadIdx.x < w) s_x[threadIdx.x] = A.x[c0 + threadIdx.x];
-    __syncthreads();
-    const size_t k = global_tid();
-    if (k >= (size_t)c0) return;
-    double s = A.S[n * n + k];
-    for (int i = w - 1; i >= 0; --i) s -= A.S[(size_t)(c0 + i) * n + k] * s_x[i];
-    A.S[n * n + k] = s;
-}
+// what its kernels read of the workspace
+struct SystemView {
+    double *S, *x;
+    int* fail;
+    const int* nf;
+    __device__ size_t n() const { return 6 * (size_t)*nf; }
+};
 
 // ------------------------------------------------------------------ the step, the trial, the judge
 
@@ -917,6 +805,9 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
     a.delta_mono = (double)dm, a.delta_stereo = (double)ds;
     a.dsqr_mono = (double)(float)((double)dm * (double)dm), a.dsqr_stereo = (double)(float)((double)ds * (double)ds);
 
+    SystemView view;
+    view.S = a.S, view.x = a.x, view.fail = &a.ctl->fail, view.nf = &a.ctl->nf;
+
     const size_t P = L.P, M = L.M, E = L.E;
     const dim3 T(kThreads);
 #define LAUNCH(kernel, grid, block, ...)                                       \
@@ -959,21 +850,7 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
                 LAUNCH(ba_edge_bd, dim3(blocks_for(E)), T, a);
                 if (nf) {
                     LAUNCH(ba_schur, dim3(blocks_for((size_t)nf * nf * 36 + n)), T, a);
-                    for (size_t c0 = 0; c0 < n; c0 += kNB) {
-                        const int w = (int)(n - c0 < (size_t)kNB ? n - c0 : (size_t)kNB);
-                        const size_t below = n + 1 - (c0 + w);  // rows under the block, b_schur's included
-                        LAUNCH(ba_chol_diag, dim3(1), dim3(64), a, (int)c0, w);
-                        LAUNCH(ba_chol_panel, dim3(blocks_for(below, kRows)), dim3(kRows), a, (int)c0, w);
-                        if (c0 + w == n) break;  // no column is left
-                        const unsigned tiles = blocks_for(below, kTile);
-                        LAUNCH(ba_chol_update, dim3(tiles, tiles), dim3(kTile * kTile), a, (int)c0, w);
-                    }
-                    for (size_t c0 = ((n - 1) / kNB) * kNB;; c0 -= kNB) {
-                        const int w = (int)(n - c0 < (size_t)kNB ? n - c0 : (size_t)kNB);
-                        LAUNCH(ba_back_diag, dim3(1), dim3(64), a, (int)c0, w);
-                        if (c0 == 0) break;
-                        LAUNCH(ba_back_rows, dim3(blocks_for(c0)), T, a, (int)c0, w);
-                    }
+                    ORB_HIP(orbgpu::chol::enqueue_solve(view, n, st));
                 }
                 LAUNCH(ba_point_x, dim3(blocks_for(M)), T, a);
                 LAUNCH(ba_trial, dim3(blocks_for(P + M)), T, a);

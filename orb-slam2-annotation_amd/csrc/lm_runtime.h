@@ -31,6 +31,13 @@ __device__ inline void run_init_lambda(Run& r, double max_diag) {
     r.stop_bad = 0;
 }
 
+// computeLambdaInit under setUserLambdaInit(user_lambda > 0) (:166-169): no diagonal maximum is taken
+__device__ inline void run_init_lambda_user(Run& r, double user_lambda) {
+    r.lambda = user_lambda;
+    r.ni = 2.0;
+    r.stop_bad = 0;
+}
+
 // a build pass gave the robust chi2 at the kept estimate: the iteration begins
 __device__ inline void run_begin_iteration(Run& r, double chi) {
     r.chi = chi;
