@@ -8,7 +8,9 @@
 // over the free active vertices is dense and is solved by chol_blocked.h.
 // tests/essential_ref.py is the same arithmetic, expression for expression.
 // The Sim3 algebra is sim3opt_device.h's and sim3_log_device.h's, the LM
-// decisions are lm_runtime.h's.
+// decisions are lm_runtime.h's; the control block, the host record, the ordered
+// sums and the bodies of the begin and judge kernels are wholechip_lm.h's,
+// shared with globalba.hip.
 //
 // The calling thread drives the loop as globalba.hip's does: a phase that needs
 // the previous one complete is the next launch on the stream; no kernel
@@ -44,13 +46,19 @@
 #include "chol_blocked.h"
 #include "host_common.h"
 #include "host_ctx.h"
-#include "lm_runtime.h"
 #include "sim3_log_device.h"
+#include "wholechip_lm.h"
 
 namespace {
 
 namespace lm = orbgpu::lm;
 namespace chol = orbgpu::chol;
+namespace wc = orbgpu::wholechip;
+using wc::block_total;
+using wc::blocks_for;
+using wc::global_tid;
+using wc::HostRec;
+using wc::kCtlBytes;
 using orbgpu::sim3opt::Sim3;
 using orbgpu::sim3opt::sim3_exp;
 using orbgpu::sim3opt::sim3_inverse;
@@ -74,20 +82,7 @@ constexpr int kEdgeProducts = 3 * 49 + 2 * 7;
 // ints per vertex
 constexpr int IV_HIDX = 0, IV_HLIST = 1, IV_START = 2, IV_COUNT = 3, IV_FREE = 4, kVertI = 5;
 
-// the optimisation's state on the device; zeroed by the call, then written by one lane of one kernel at a time
-struct Ctl {
-    lm::Run run;
-    double first_chi;
-    int bad, fail, nf, n_active;
-};
-constexpr size_t kCtlBytes = 256;
-static_assert(sizeof(Ctl) <= kCtlBytes, "Ctl outgrew its slot");
-
-// what the host reads after a synchronisation (coherent pinned memory)
-struct HostRec {
-    double chi, first_chi, lambda;
-    int bad, nf, n_active, solved, accepted, more, done, iter, rejected, pad;
-};
+using Ctl = wc::CtlBase;  // nothing of its own
 
 struct Layout {
     size_t N, E, n_max;                          // n_max = 7 N
@@ -190,28 +185,6 @@ __device__ inline double chi2_of(const double (&e)[7]) {
     for (int k = 1; k < 7; ++k) c = c + e[k] * e[k];
     return c;
 }
-
-// the workgroup's sum of one value per lane in lane order, in lane 0: 16 lanes add 16 values each,
-// lane 0 adds the 16 sums (globalba.hip's)
-__device__ inline double block_total(double v, double (&s_val)[kThreads], double (&s_row)[16]) {
-    const int tid = threadIdx.x;
-    s_val[tid] = v;
-    __syncthreads();
-    if (tid < 16) {
-        double s = s_val[16 * tid];
-        for (int k = 1; k < 16; ++k) s += s_val[16 * tid + k];
-        s_row[tid] = s;
-    }
-    __syncthreads();
-    double s = 0.0;
-    if (tid == 0) {
-        s = s_row[0];
-        for (int k = 1; k < 16; ++k) s += s_row[k];
-    }
-    return s;
-}
-
-__device__ inline size_t global_tid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
 // ------------------------------------------------------------------ once per call: check and structure
 
@@ -460,27 +433,11 @@ __global__ __launch_bounds__(kThreads) void eg_vertex_b(Args A) {
     VD(V_B + r, v) = acc;
 }
 
-// the sum of n per-workgroup partial sums in workgroup order
-__device__ inline double ordered_sum(const double* part, int n) {
-    double s = 0.0;
-    if (n > 0) {
-        s = part[0];
-        for (int k = 1; k < n; ++k) s += part[k];
-    }
-    return s;
-}
-
 // the iteration begins: chi2 at the kept estimates; lambda = 1e-16 in the first
 __global__ void eg_begin(Args A, int first) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    Ctl& c = *A.ctl;
-    const double chi = ordered_sum(A.chi_part, A.n_chi);
-    if (first) {
-        lm::run_init_lambda_user(c.run, kLambdaInit);
-        c.first_chi = chi;
-    }
-    lm::run_begin_iteration(c.run, chi);
-    c.fail = 0;
+    wc::begin_iteration(*A.ctl, A.chi_part, A.n_chi, first,
+                        [](lm::Run& run) { lm::run_init_lambda_user(run, kLambdaInit); });
 }
 
 // ------------------------------------------------------------------ per trial
@@ -560,19 +517,7 @@ __global__ __launch_bounds__(kThreads) void eg_trial(Args A) {
 // OptimizationAlgorithmLevenberg::solve's decisions after a trial, by one lane; the host reads rec
 __global__ void eg_judge(Args A, int max_iter) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    Ctl& c = *A.ctl;
-    const bool solved = !c.fail;
-    const double tmp_chi = solved ? ordered_sum(A.chi_part, A.n_chi) : 0.0;
-    const double ssum = solved ? ordered_sum(A.scale_part, A.n_scale) : 0.0;
-    const bool accepted = lm::run_judge(c.run, solved, tmp_chi, ssum);
-    const bool more = lm::run_more_trials(c.run);
-    const bool done = more ? false : lm::run_end_iteration(c.run, max_iter);
-    c.fail = 0;
-    HostRec* rec = A.rec;
-    rec->chi = c.run.chi, rec->first_chi = c.first_chi, rec->lambda = c.run.lambda;
-    rec->solved = solved, rec->accepted = accepted, rec->more = more, rec->done = done;
-    rec->iter = c.run.iter, rec->rejected = c.run.rejected;
-    __threadfence_system();
+    wc::judge(*A.ctl, A.rec, A.chi_part, A.n_chi, A.scale_part, A.n_scale, max_iter);
 }
 
 // an accepted trial becomes the estimate
@@ -624,24 +569,6 @@ __global__ __launch_bounds__(kThreads) void eg_write(Args A) {
 
 // ------------------------------------------------------------------ host
 
-inline unsigned blocks_for(size_t lanes, int threads = kThreads) {
-    return (unsigned)((lanes + threads - 1) / threads);
-}
-
-// the calling thread's record, allocated at its first call and kept
-struct PinnedRec {
-    HostRec* p = nullptr;
-    ~PinnedRec() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-int host_rec(HostRec** out) {
-    thread_local PinnedRec r;
-    if (!r.p) ORB_HIP(hipHostMalloc((void**)&r.p, sizeof(HostRec), hipHostMallocCoherent));
-    *out = r.p;
-    return ORBGPU_OK;
-}
-
 int check_args(int n_kf, int n_edges, int n_points, int n_iterations, bool kf_arrays, bool edge_arrays,
                bool point_arrays, bool result) {
     using orbgpu::fail;
@@ -679,7 +606,7 @@ extern "C" int orbgpu_optimize_essential_graph_device(
     (void)hipGetLastError();
     std::memset(result, 0, sizeof(*result));
     HostRec* rec;
-    if (int rc = host_rec(&rec)) return rc;
+    if (int rc = wc::host_rec(&rec)) return rc;
     std::memset(rec, 0, sizeof(*rec));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
@@ -702,19 +629,13 @@ extern "C" int orbgpu_optimize_essential_graph_device(
 
     const size_t N = L.N, E = L.E, M = (size_t)n_points;
     const dim3 T(kThreads);
-#define LAUNCH(kernel, grid, block, ...)                                       \
-    do {                                                                       \
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);           \
-        ORB_HIP(hipGetLastError());                                            \
-    } while (0)
-
     // once per call: the check, the estimates and the structure; one synchronisation
     ORB_HIP(hipMemsetAsync(a.ctl, 0, kCtlBytes, st));
-    if (E + M) LAUNCH(eg_check, dim3(blocks_for(E > M ? E : M)), T, a);
-    if (N) LAUNCH(eg_init, dim3(blocks_for(N)), T, a);
-    if (E) LAUNCH(eg_measure, dim3(blocks_for(E)), T, a);
-    LAUNCH(eg_scan, dim3(1), dim3(64), a);
-    if (E && N) LAUNCH(eg_lists, dim3(blocks_for(N, kThreads / 64)), T, a);
+    if (E + M) ORB_LAUNCH(st, eg_check, dim3(blocks_for(E > M ? E : M)), T, a);
+    if (N) ORB_LAUNCH(st, eg_init, dim3(blocks_for(N)), T, a);
+    if (E) ORB_LAUNCH(st, eg_measure, dim3(blocks_for(E)), T, a);
+    ORB_LAUNCH(st, eg_scan, dim3(1), dim3(64), a);
+    if (E && N) ORB_LAUNCH(st, eg_lists, dim3(blocks_for(N, kThreads / 64)), T, a);
     ORB_HIP(hipStreamSynchronize(st));
     if (rec->bad) {
         result->status = -1;
@@ -728,30 +649,29 @@ extern "C" int orbgpu_optimize_essential_graph_device(
     bool done = false;
     if (nf > 0) {  // optimize() does nothing without a free active vertex
         for (int it = 0; it < n_iterations && !done; ++it) {
-            LAUNCH(eg_perturb, dim3(blocks_for(N * 15)), T, a);
-            LAUNCH(eg_error<true>, dim3(blocks_for(E)), T, a);
-            LAUNCH(eg_jacobian, dim3(blocks_for(E * 14)), T, a);
-            LAUNCH(eg_products, dim3(blocks_for(E * kEdgeProducts)), T, a);
-            LAUNCH(eg_vertex_b, dim3(blocks_for(N * 7)), T, a);
-            LAUNCH(eg_begin, dim3(1), dim3(64), a, it == 0 ? 1 : 0);
+            ORB_LAUNCH(st, eg_perturb, dim3(blocks_for(N * 15)), T, a);
+            ORB_LAUNCH(st, eg_error<true>, dim3(blocks_for(E)), T, a);
+            ORB_LAUNCH(st, eg_jacobian, dim3(blocks_for(E * 14)), T, a);
+            ORB_LAUNCH(st, eg_products, dim3(blocks_for(E * kEdgeProducts)), T, a);
+            ORB_LAUNCH(st, eg_vertex_b, dim3(blocks_for(N * 7)), T, a);
+            ORB_LAUNCH(st, eg_begin, dim3(1), dim3(64), a, it == 0 ? 1 : 0);
             iterations = it + 1;
             for (int trial = 0; trial < lm::kMaxTrials; ++trial) {
-                LAUNCH(eg_assemble, dim3(blocks_for((n + 1) * n)), T, a);
+                ORB_LAUNCH(st, eg_assemble, dim3(blocks_for((n + 1) * n)), T, a);
                 ORB_HIP(chol::enqueue_solve(view, n, st));
-                LAUNCH(eg_trial, dim3(blocks_for(N)), T, a);
-                LAUNCH(eg_error<false>, dim3(blocks_for(E)), T, a);
-                LAUNCH(eg_judge, dim3(1), dim3(64), a, n_iterations);
+                ORB_LAUNCH(st, eg_trial, dim3(blocks_for(N)), T, a);
+                ORB_LAUNCH(st, eg_error<false>, dim3(blocks_for(E)), T, a);
+                ORB_LAUNCH(st, eg_judge, dim3(1), dim3(64), a, n_iterations);
                 ORB_HIP(hipStreamSynchronize(st));
-                if (rec->accepted) LAUNCH(eg_accept, dim3(blocks_for(N * 8)), T, a);
+                if (rec->accepted) ORB_LAUNCH(st, eg_accept, dim3(blocks_for(N * 8)), T, a);
                 if (!rec->more) break;
             }
             // run_end_iteration also ends at iter >= n_iterations: the loop's own bound
             done = rec->done != 0;
         }
     }
-    if (N + M) LAUNCH(eg_write, dim3(blocks_for(N > M ? N : M)), T, a);
+    if (N + M) ORB_LAUNCH(st, eg_write, dim3(blocks_for(N > M ? N : M)), T, a);
     ORB_HIP(hipStreamSynchronize(st));
-#undef LAUNCH
     result->iterations = iterations;
     result->rejected = rec->rejected;
     result->first_chi2 = rec->first_chi, result->last_chi2 = rec->chi, result->last_lambda = rec->lambda;

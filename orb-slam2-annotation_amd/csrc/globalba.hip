@@ -6,10 +6,15 @@
 // the active set of initializeOptimization(0) -- as one launch per phase, and a
 // dense blocked Cholesky of the reduced system that runs over all compute units
 // (chol_blocked.h, shared with essential.hip).
-// tests/globalba_ref.py is the same arithmetic, expression for expression.  The
-// edge arithmetic and se3_exp_times are repeated from localba.hip, as that file
-// repeats poseopt.hip's; Huber, the quaternion algebra, Rodrigues and the pose
-// write-out are lm_device.h's; the LM decisions are lm_runtime.h's.
+// tests/globalba_ref.py is the same arithmetic, expression for expression.
+// SE3Quat is se3_device.h's, the Huber thresholds are projection_edge.h's and
+// the field offsets ba_schur_device.h's, shared with localba.hip; the control
+// block, the host record, the ordered sums and the bodies of the begin and
+// judge kernels are wholechip_lm.h's, shared with essential.hip; the pose
+// write-out is lm_device.h's, the LM decisions are lm_runtime.h's.  The
+// kernels keep their own bodies over this file's Args: the per-item arithmetic
+// is ba_schur_device.h's text, and moving the kernels onto its view measured
+// 0.5-0.9 % slower in ba_schur for a reason that was not found.
 //
 // The calling thread drives the loop.  A phase that needs the previous one
 // complete is the next launch on the stream; no kernel synchronises with
@@ -51,40 +56,38 @@
 #include <string>
 
 #include "../../include/orbgpu_globalba.h"
+#include "ba_schur_device.h"
 #include "chol_blocked.h"
 #include "host_common.h"
 #include "host_ctx.h"
-#include "lm_runtime.h"
+#include "wholechip_lm.h"
 
 namespace {
 
 namespace lm = orbgpu::lm;
+namespace wc = orbgpu::wholechip;
+using namespace orbgpu::ba;  // the field offsets
+using lm::upper_jk;
+using orbgpu::se3::quat_to_R;
+using orbgpu::se3::se3_exp_times;
+using wc::block_total;
+using wc::blocks_for;
+using wc::global_tid;
+using wc::HostRec;
+using wc::kCtlBytes;
 
 constexpr int kThreads = 256;
+constexpr int kEdgeD = 67, kPointI = 2;  // doubles per edge, ints per point: ba_schur_device.h's fields alone
 
-// doubles per pose, point and edge in the workspace, and where each field starts (localba.hip's)
-constexpr int P_EST = 0, P_TRIAL = 7, P_H = 14, kPoseD = 41;                                   // q t | q t | H 21, b 6
-constexpr int L_EST = 0, L_TRIAL = 3, L_H = 6, L_DINV = 15, L_V = 21, L_X = 24, kPointD = 27;  // H 6, b 3
-constexpr int E_JP = 0, E_JL = 18, E_W = 27, E_OMR = 28, E_B = 31, E_BD = 49, kEdgeD = 67;
-// ints per pose, point and edge
-constexpr int IP_HIDX = 0, IP_HLIST = 1, IP_START = 2, IP_COUNT = 3, IP_FREE = 4, kPoseI = 5;
-constexpr int IL_FIRST = 0, IL_END = 1, kPointI = 2;
-
-// the optimisation's state on the device; zeroed by the call, then written by one lane of one kernel at a time
+// the optimisation's state on the device (wholechip::CtlBase's members and computeLambdaInit's maximum);
+// zeroed by the call, then written by one lane of one kernel at a time
 struct Ctl {
     lm::Run run;
     unsigned long long max_bits;  // computeLambdaInit's maximum, as bits
     double first_chi;
     int bad, fail, nf, n_active;
 };
-constexpr size_t kCtlBytes = 256;
 static_assert(sizeof(Ctl) <= kCtlBytes, "Ctl outgrew its slot");
-
-// what the host reads after a synchronisation (coherent pinned memory)
-struct HostRec {
-    double chi, first_chi, lambda;
-    int bad, nf, n_active, solved, accepted, more, done, iter, rejected, pad;
-};
 
 struct Layout {
     size_t P, M, E, n_max;                            // n_max = 6 P
@@ -143,88 +146,6 @@ struct Args {
 #define PI(f, p) A.ip[(size_t)(f) * A.P + (p)]
 #define LI(f, m) A.il[(size_t)(f) * A.M + (m)]
 
-// ------------------------------------------------------------------ SE3Quat (one lane per pose), as localba.hip's
-
-// SE3Quat::normalizeRotation
-__device__ inline void quat_normalize(double (&q)[4]) {
-    if (q[3] < 0) {
-        for (int i = 0; i < 4; ++i) q[i] = -q[i];
-    }
-    const double n = __dsqrt_rn(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
-}
-
-// SE3Quat::exp(x) * (q, t)  (se3quat.h:223-257, 104-110)
-__device__ void se3_exp_times(const double (&eq)[4], const double (&et)[3], const double (&x)[6], double (&oq)[4],
-                              double (&ot)[3]) {
-    double O[3][3], O2[3][3], R[9], V[3][3];
-    const double theta = lm::rodrigues(x[0], x[1], x[2], O, O2, R);
-    if (theta < lm::kSmallAngle) {
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) V[i][j] = R[3 * i + j];
-    } else {
-        const double sn = sin(theta), cs = cos(theta);
-        const double b = (1.0 - cs) / (theta * theta);
-        const double d = (theta - sn) / ((theta * theta) * theta);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) V[i][j] = ((i == j ? 1.0 : 0.0) + b * O[i][j]) + d * O2[i][j];
-    }
-    double te[3];
-    for (int i = 0; i < 3; ++i) te[i] = (V[i][0] * x[3] + V[i][1] * x[4]) + V[i][2] * x[5];
-    double a[4];
-    lm::quat_from_R(R, a);
-    quat_normalize(a);
-    double r0, r1, r2;
-    lm::quat_rotate(a, et[0], et[1], et[2], r0, r1, r2);
-    lm::quat_mul(a, eq, oq);
-    quat_normalize(oq);
-    ot[0] = te[0] + r0;
-    ot[1] = te[1] + r1;
-    ot[2] = te[2] + r2;
-}
-
-// Eigen's Quaternion::toRotationMatrix, as lm::write_T16 has it
-__device__ inline void quat_to_R(const double (&q)[4], double (&R)[3][3]) {
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0][0] = 1.0 - (tyy + tzz), R[0][1] = txy - twz, R[0][2] = txz + twy;
-    R[1][0] = txy + twz, R[1][1] = 1.0 - (txx + tzz), R[1][2] = tyz - twx;
-    R[2][0] = txz - twy, R[2][1] = tyz + twx, R[2][2] = 1.0 - (txx + tyy);
-}
-
-// (j, k), j <= k, of upper entry v of an N x N block (row by row)
-template <int N>
-__device__ inline void upper_jk(int v, int& j, int& k) {
-    j = 0;
-    while (v >= N - j) v -= N - j, ++j;
-    k = j + v;
-}
-
-// the workgroup's sum of one value per lane in lane order, in lane 0: 16 lanes add 16 values each,
-// lane 0 adds the 16 sums
-__device__ inline double block_total(double v, double (&s_val)[kThreads], double (&s_row)[16]) {
-    const int tid = threadIdx.x;
-    s_val[tid] = v;
-    __syncthreads();
-    if (tid < 16) {
-        double s = s_val[16 * tid];
-        for (int k = 1; k < 16; ++k) s += s_val[16 * tid + k];
-        s_row[tid] = s;
-    }
-    __syncthreads();
-    double s = 0.0;
-    if (tid == 0) {
-        s = s_row[0];
-        for (int k = 1; k < 16; ++k) s += s_row[k];
-    }
-    return s;
-}
-
-__device__ inline size_t global_tid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
-
 // ------------------------------------------------------------------ once per call: check and structure
 
 // an edge index out of range or edge_point decreasing: nothing else may index with these arrays
@@ -240,14 +161,10 @@ __global__ __launch_bounds__(kThreads) void ba_init(Args A) {
     const size_t i = global_tid();
     if (i < (size_t)A.P) {
         const int p = (int)i;
-        const float* Tp = A.Tcw + 12 * i;
-        double R[9], q[4];
-        for (int r = 0; r < 3; ++r)
-            for (int col = 0; col < 3; ++col) R[3 * r + col] = (double)Tp[4 * r + col];
-        lm::quat_from_R(R, q);
-        quat_normalize(q);
+        double q[4], t[3];
+        orbgpu::se3::pose_from_T12(A.Tcw + 12 * i, q, t);
         for (int k = 0; k < 4; ++k) PD(P_EST + k, p) = q[k];
-        for (int r = 0; r < 3; ++r) PD(P_EST + 4 + r, p) = (double)Tp[4 * r + 3];
+        for (int r = 0; r < 3; ++r) PD(P_EST + 4 + r, p) = t[r];
         PI(IP_COUNT, p) = 0;
     }
     if (i < (size_t)A.M) {
@@ -485,27 +402,13 @@ __global__ __launch_bounds__(kThreads) void ba_vertex_sums(Args A, int first) {
     LD(L_H + v, m) = acc;
 }
 
-// the sum of n per-workgroup partial sums in workgroup order
-__device__ inline double ordered_sum(const double* part, int n) {
-    double s = 0.0;
-    if (n > 0) {
-        s = part[0];
-        for (int k = 1; k < n; ++k) s += part[k];
-    }
-    return s;
-}
-
 // the iteration begins: the robust chi2 at the kept estimates, computeLambdaInit in the first
 __global__ void ba_begin(Args A, int first) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     Ctl& c = *A.ctl;
-    const double chi = ordered_sum(A.chi_part, A.n_chi);
-    if (first) {
-        lm::run_init_lambda(c.run, __longlong_as_double((long long)c.max_bits));
-        c.first_chi = chi;
-    }
-    lm::run_begin_iteration(c.run, chi);
-    c.fail = 0;
+    wc::begin_iteration(c, A.chi_part, A.n_chi, first, [&c](lm::Run& run) {
+        lm::run_init_lambda(run, __longlong_as_double((long long)c.max_bits));
+    });
 }
 
 // Dinv = (Hll + lambda I)^-1 from cofactors and Dinv b_l, one lane per point
@@ -684,19 +587,7 @@ __global__ __launch_bounds__(kThreads) void ba_trial(Args A) {
 // OptimizationAlgorithmLevenberg::solve's decisions after a trial, by one lane; the host reads rec
 __global__ void ba_judge(Args A, int max_iter) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    Ctl& c = *A.ctl;
-    const bool solved = !c.fail;
-    const double tmp_chi = solved ? ordered_sum(A.chi_part, A.n_chi) : 0.0;
-    const double ssum = ordered_sum(A.scale_part, A.n_scale);
-    const bool accepted = lm::run_judge(c.run, solved, tmp_chi, ssum);
-    const bool more = lm::run_more_trials(c.run);
-    const bool done = more ? false : lm::run_end_iteration(c.run, max_iter);
-    c.fail = 0;
-    HostRec* rec = A.rec;
-    rec->chi = c.run.chi, rec->first_chi = c.first_chi, rec->lambda = c.run.lambda;
-    rec->solved = solved, rec->accepted = accepted, rec->more = more, rec->done = done;
-    rec->iter = c.run.iter, rec->rejected = c.run.rejected;
-    __threadfence_system();
+    wc::judge(*A.ctl, A.rec, A.chi_part, A.n_chi, A.scale_part, A.n_scale, max_iter);
 }
 
 // an accepted trial becomes the estimate
@@ -726,24 +617,6 @@ __global__ __launch_bounds__(kThreads) void ba_write(Args A) {
 #undef LI
 
 // ------------------------------------------------------------------ host
-
-inline unsigned blocks_for(size_t lanes, int threads = kThreads) {
-    return (unsigned)((lanes + threads - 1) / threads);
-}
-
-// the calling thread's record, allocated at its first call and kept
-struct PinnedRec {
-    HostRec* p = nullptr;
-    ~PinnedRec() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-int host_rec(HostRec** out) {
-    thread_local PinnedRec r;
-    if (!r.p) ORB_HIP(hipHostMalloc((void**)&r.p, sizeof(HostRec), hipHostMallocCoherent));
-    *out = r.p;
-    return ORBGPU_OK;
-}
 
 int check_args(int n_poses, int n_points, int n_edges, int n_iterations, bool pose_arrays, bool point_arrays,
                bool edge_arrays, bool result) {
@@ -783,7 +656,7 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
     (void)hipGetLastError();
     std::memset(result, 0, sizeof(*result));
     HostRec* rec;
-    if (int rc = host_rec(&rec)) return rc;
+    if (int rc = wc::host_rec(&rec)) return rc;
     std::memset(rec, 0, sizeof(*rec));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
@@ -800,29 +673,22 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
     int* ints = reinterpret_cast<int*>(base + L.ints);
     a.ip = ints + L.pose_i, a.il = ints + L.point_i, a.ie = ints + L.edge_i;
     a.n_chi = (int)L.n_chi, a.n_scale = (int)L.n_scale;
-    // Optimizer.cpp:112-113; robust_kernel_impl.h:85: float dsqr = delta * delta (delta a double)
-    const float dm = (float)std::sqrt(5.99), ds = (float)std::sqrt(7.815);
-    a.delta_mono = (double)dm, a.delta_stereo = (double)ds;
-    a.dsqr_mono = (double)(float)((double)dm * (double)dm), a.dsqr_stereo = (double)(float)((double)ds * (double)ds);
+    const auto hc = orbgpu::proj_edge::huber_constants(5.99, 7.815);  // Optimizer.cpp:112-113
+    a.delta_mono = hc.delta_mono, a.delta_stereo = hc.delta_stereo;
+    a.dsqr_mono = hc.dsqr_mono, a.dsqr_stereo = hc.dsqr_stereo;
 
     SystemView view;
     view.S = a.S, view.x = a.x, view.fail = &a.ctl->fail, view.nf = &a.ctl->nf;
 
     const size_t P = L.P, M = L.M, E = L.E;
     const dim3 T(kThreads);
-#define LAUNCH(kernel, grid, block, ...)                                       \
-    do {                                                                       \
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);           \
-        ORB_HIP(hipGetLastError());                                            \
-    } while (0)
-
     // once per call: the check, the estimates and the structure; one synchronisation
     ORB_HIP(hipMemsetAsync(a.ctl, 0, kCtlBytes, st));
-    if (E) LAUNCH(ba_check, dim3(blocks_for(E)), T, a);
-    if (P + M) LAUNCH(ba_init, dim3(blocks_for(P > M ? P : M)), T, a);
-    if (E) LAUNCH(ba_runs, dim3(blocks_for(E)), T, a);
-    LAUNCH(ba_scan, dim3(1), dim3(64), a);
-    if (E && P) LAUNCH(ba_lists, dim3(blocks_for(P, kThreads / 64)), T, a);
+    if (E) ORB_LAUNCH(st, ba_check, dim3(blocks_for(E)), T, a);
+    if (P + M) ORB_LAUNCH(st, ba_init, dim3(blocks_for(P > M ? P : M)), T, a);
+    if (E) ORB_LAUNCH(st, ba_runs, dim3(blocks_for(E)), T, a);
+    ORB_LAUNCH(st, ba_scan, dim3(1), dim3(64), a);
+    if (E && P) ORB_LAUNCH(st, ba_lists, dim3(blocks_for(P, kThreads / 64)), T, a);
     ORB_HIP(hipStreamSynchronize(st));
     if (rec->bad) {
         result->status = -1;
@@ -841,23 +707,23 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
                 break;
             }
             if (done) break;
-            LAUNCH(ba_edges<true>, dim3(blocks_for(E)), T, a);
-            LAUNCH(ba_vertex_sums, dim3(blocks_for(P * 27 + M * 9)), T, a, it == 0 ? 1 : 0);
-            LAUNCH(ba_begin, dim3(1), dim3(64), a, it == 0 ? 1 : 0);
+            ORB_LAUNCH(st, ba_edges<true>, dim3(blocks_for(E)), T, a);
+            ORB_LAUNCH(st, ba_vertex_sums, dim3(blocks_for(P * 27 + M * 9)), T, a, it == 0 ? 1 : 0);
+            ORB_LAUNCH(st, ba_begin, dim3(1), dim3(64), a, it == 0 ? 1 : 0);
             iterations = it + 1;
             for (int trial = 0; trial < lm::kMaxTrials; ++trial) {
-                LAUNCH(ba_point_inverse, dim3(blocks_for(M)), T, a);
-                LAUNCH(ba_edge_bd, dim3(blocks_for(E)), T, a);
+                ORB_LAUNCH(st, ba_point_inverse, dim3(blocks_for(M)), T, a);
+                ORB_LAUNCH(st, ba_edge_bd, dim3(blocks_for(E)), T, a);
                 if (nf) {
-                    LAUNCH(ba_schur, dim3(blocks_for((size_t)nf * nf * 36 + n)), T, a);
+                    ORB_LAUNCH(st, ba_schur, dim3(blocks_for((size_t)nf * nf * 36 + n)), T, a);
                     ORB_HIP(orbgpu::chol::enqueue_solve(view, n, st));
                 }
-                LAUNCH(ba_point_x, dim3(blocks_for(M)), T, a);
-                LAUNCH(ba_trial, dim3(blocks_for(P + M)), T, a);
-                LAUNCH(ba_edges<false>, dim3(blocks_for(E)), T, a);
-                LAUNCH(ba_judge, dim3(1), dim3(64), a, n_iterations);
+                ORB_LAUNCH(st, ba_point_x, dim3(blocks_for(M)), T, a);
+                ORB_LAUNCH(st, ba_trial, dim3(blocks_for(P + M)), T, a);
+                ORB_LAUNCH(st, ba_edges<false>, dim3(blocks_for(E)), T, a);
+                ORB_LAUNCH(st, ba_judge, dim3(1), dim3(64), a, n_iterations);
                 ORB_HIP(hipStreamSynchronize(st));
-                if (rec->accepted) LAUNCH(ba_accept, dim3(blocks_for(P * 7 > M * 3 ? P * 7 : M * 3)), T, a);
+                if (rec->accepted) ORB_LAUNCH(st, ba_accept, dim3(blocks_for(P * 7 > M * 3 ? P * 7 : M * 3)), T, a);
                 if (!rec->more) break;
                 if (flag_set(stop_flag)) {  // optimization_algorithm_levenberg.cpp:149
                     stopped = 2;
@@ -869,9 +735,8 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
             done = rec->done != 0;
         }
     }
-    if (P + M) LAUNCH(ba_write, dim3(blocks_for(P > M ? P : M)), T, a);
+    if (P + M) ORB_LAUNCH(st, ba_write, dim3(blocks_for(P > M ? P : M)), T, a);
     ORB_HIP(hipStreamSynchronize(st));
-#undef LAUNCH
     result->iterations = iterations;
     result->rejected = rec->rejected;
     result->stopped = stopped;

@@ -31,6 +31,13 @@ template <int N>
 __host__ __device__ constexpr int upper_index(int j, int k) {
     return j * N - j * (j - 1) / 2 + (k - j);
 }
+// its inverse: (j, k), j <= k, of upper entry v
+template <int N>
+__device__ inline void upper_jk(int v, int& j, int& k) {
+    j = 0;
+    while (v >= N - j) v -= N - j, ++j;
+    k = j + v;
+}
 // index of L(i, j), j <= i, in the lower triangle (row by row)
 __host__ __device__ constexpr int lower_index(int i, int j) { return i * (i + 1) / 2 + j; }
 

@@ -7,8 +7,14 @@
 // back-substitution (core/block_solver.hpp:355-487, 565-610), g2o's
 // Levenberg-Marquardt over the whole vector and the active set of
 // initializeOptimization(0).  tests/localba_ref.py is the same arithmetic,
-// expression for expression.  Huber, the quaternion algebra, Rodrigues and the
-// pose write-out are lm_device.h's; the LM decisions are lm_runtime.h's.
+// expression for expression.  The arithmetic of one edge, pose or point -- the
+// edges, the vertex blocks, Dinv, B Dinv, b_schur, the back-substitution, oplus
+// -- and the workspace's field offsets are ba_schur_device.h's (over
+// projection_edge.h and se3_device.h), shared with globalba.hip; Huber, the
+// quaternion algebra and the pose write-out are lm_device.h's, the LM decisions
+// lm_runtime.h's, the lane-order sum wholechip_lm.h's.  This file keeps the
+// structure build, the assembly of S by half-row owners, the in-kernel column
+// Cholesky, computeLambdaInit's maximum and the two rounds with their flagging.
 //
 // One workgroup per job, one launch for the whole call, no synchronisation
 // between workgroups.  Everything a job keeps lives in its slice of the
@@ -39,23 +45,25 @@
 #include "../../include/orbgpu_localba.h"
 #include "host_common.h"
 #include "host_ctx.h"
+#include "ba_schur_device.h"
 #include "lm_runtime.h"
+#include "wholechip_lm.h"
 
 namespace {
 
 namespace lm = orbgpu::lm;
+namespace ba = orbgpu::ba;
+using namespace orbgpu::ba;  // the field offsets
+using orbgpu::proj_edge::HuberConst;
 
 constexpr int kThreads = 256;
 constexpr int kIterations[2] = {5, 10};  // optimizer.optimize(5), optimize(10): Optimizer.cpp:760, 809
 
-// doubles per pose, point and edge in the workspace, and where each field starts
-constexpr int P_EST = 0, P_TRIAL = 7, P_H = 14, kPoseD = 41;                             // q t | q t | H 21, b 6
-constexpr int L_EST = 0, L_TRIAL = 3, L_H = 6, L_DINV = 15, L_V = 21, L_X = 24, kPointD = 27;  // H 6, b 3
-constexpr int E_JP = 0, E_JL = 18, E_W = 27, E_OMR = 28, E_B = 31, E_BD = 49, E_CHI = 67, kEdgeD = 68;
+// this file's fields beside ba_schur_device.h's: an edge's chi2 as the edge holds it, whether a point
+// is active, and per edge its entry of the pose-major list and its level
+constexpr int E_CHI = 67, kEdgeD = 68;
 constexpr int kSysVecs = 5;  // column residues, diagonal of L, running sums, y, x
-// ints per pose, point and edge
-constexpr int IP_HIDX = 0, IP_HLIST = 1, IP_START = 2, IP_COUNT = 3, IP_FREE = 4, kPoseI = 5;
-constexpr int IL_FIRST = 0, IL_END = 1, IL_ACTIVE = 2, kPointI = 3;
+constexpr int IL_ACTIVE = 2, kPointI = 3;
 constexpr int IE_LIST = 0, IE_LEVEL = 1, kEdgeI = 2;
 
 struct Layout {
@@ -93,7 +101,7 @@ struct Args {
     uint8_t* erase;
     orbgpu_localba_result* results;
     double* ws;
-    double delta_mono, delta_stereo, dsqr_mono, dsqr_stereo;
+    HuberConst hc;
 };
 
 // every condition on a job's counts and ranges; host and device
@@ -116,82 +124,10 @@ struct Ctl {
     int nf, n_active, solved, accepted, more, done, n_flag;
 };
 
-// ------------------------------------------------------------------ SE3Quat (one lane per pose)
-
-// SE3Quat::normalizeRotation
-__device__ inline void quat_normalize(double (&q)[4]) {
-    if (q[3] < 0) {
-        for (int i = 0; i < 4; ++i) q[i] = -q[i];
-    }
-    const double n = __dsqrt_rn(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
-}
-
-// SE3Quat::exp(x) * (q, t)  (se3quat.h:223-257, 104-110), as poseopt.hip's
-__device__ void se3_exp_times(const double (&eq)[4], const double (&et)[3], const double (&x)[6], double (&oq)[4],
-                              double (&ot)[3]) {
-    double O[3][3], O2[3][3], R[9], V[3][3];
-    const double theta = lm::rodrigues(x[0], x[1], x[2], O, O2, R);
-    if (theta < lm::kSmallAngle) {
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) V[i][j] = R[3 * i + j];
-    } else {
-        const double sn = sin(theta), cs = cos(theta);
-        const double b = (1.0 - cs) / (theta * theta);
-        const double d = (theta - sn) / ((theta * theta) * theta);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) V[i][j] = ((i == j ? 1.0 : 0.0) + b * O[i][j]) + d * O2[i][j];
-    }
-    double te[3];
-    for (int i = 0; i < 3; ++i) te[i] = (V[i][0] * x[3] + V[i][1] * x[4]) + V[i][2] * x[5];
-    double a[4];
-    lm::quat_from_R(R, a);
-    quat_normalize(a);
-    double r0, r1, r2;
-    lm::quat_rotate(a, et[0], et[1], et[2], r0, r1, r2);
-    lm::quat_mul(a, eq, oq);
-    quat_normalize(oq);
-    ot[0] = te[0] + r0;
-    ot[1] = te[1] + r1;
-    ot[2] = te[2] + r2;
-}
-
-// Eigen's Quaternion::toRotationMatrix, as lm::write_T16 has it
-__device__ inline void quat_to_R(const double (&q)[4], double (&R)[3][3]) {
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0][0] = 1.0 - (tyy + tzz), R[0][1] = txy - twz, R[0][2] = txz + twy;
-    R[1][0] = txy + twz, R[1][1] = 1.0 - (txx + tzz), R[1][2] = tyz - twx;
-    R[2][0] = txz - twy, R[2][1] = tyz + twx, R[2][2] = 1.0 - (txx + tyy);
-}
-
-// (j, k), j <= k, of upper entry v of an N x N block (row by row)
-template <int N>
-__device__ inline void upper_jk(int v, int& j, int& k) {
-    j = 0;
-    while (v >= N - j) v -= N - j, ++j;
-    k = j + v;
-}
-
-// sum of one value per lane in lane order: 16 lanes add 16 values each, lane 0 adds the 16 sums
-__device__ inline double block_total(double v, double (&s_val)[kThreads], double (&s_row)[16], Ctl& c) {
-    const int tid = threadIdx.x;
-    s_val[tid] = v;
-    __syncthreads();
-    if (tid < 16) {
-        double s = s_val[16 * tid];
-        for (int k = 1; k < 16; ++k) s += s_val[16 * tid + k];
-        s_row[tid] = s;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double s = s_row[0];
-        for (int k = 1; k < 16; ++k) s += s_row[k];
-        c.total = s;
-    }
+// wholechip::block_total, its total broadcast to every lane through c.total
+__device__ inline double job_total(double v, double (&s_val)[kThreads], double (&s_row)[16], Ctl& c) {
+    const double s = orbgpu::wholechip::block_total(v, s_val, s_row);
+    if (threadIdx.x == 0) c.total = s;
     __syncthreads();
     return c.total;
 }
@@ -240,9 +176,6 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
 
     // the job's slices of the workspace
     const Layout L = make_layout(A.batch, A.total_poses, A.total_points, A.total_edges, A.max_local);
-    double* const wp = A.ws + L.pose_d + po;    // field f of pose p: wp[f * TP + p]
-    double* const wl = A.ws + L.point_d + lo;
-    double* const we = A.ws + L.edge_d + eo;
     const size_t n_max = L.n;
     double* const S = A.ws + L.sys_d + (size_t)jb * (n_max * n_max + kSysVecs * n_max);
     double* const v_r = S + n_max * n_max;
@@ -251,226 +184,82 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
     double* const v_y = v_s + n_max;
     double* const v_x = v_y + n_max;
     int* const ibase = reinterpret_cast<int*>(A.ws + L.sys_d + (size_t)A.batch * (n_max * n_max + kSysVecs * n_max));
-    int* const ip = ibase + L.pose_i + po;
-    int* const il = ibase + L.point_i + lo;
     int* const ie = ibase + L.edge_i + eo;
-    const size_t TP = L.TP, TM = L.TM, TE = L.TE;
-#define PD(f, p) wp[(size_t)(f) * TP + (p)]
-#define LD(f, m) wl[(size_t)(f) * TM + (m)]
-#define ED(f, e) we[(size_t)(f) * TE + (e)]
-#define PI(f, p) ip[(size_t)(f) * TP + (p)]
-#define LI(f, m) il[(size_t)(f) * TM + (m)]
-#define EI(f, e) ie[(size_t)(f) * TE + (e)]
+    const size_t TE = L.TE;
+    auto EI = [ie, TE](int f, int e) -> int& { return ie[(size_t)f * TE + e]; };
+    // the strides are the call's totals, the job's offsets are in the base pointers
+    ba::View V;
+    V.wp = A.ws + L.pose_d + po, V.wl = A.ws + L.point_d + lo, V.we = A.ws + L.edge_d + eo;
+    V.ip = ibase + L.pose_i + po, V.il = ibase + L.point_i + lo, V.list = ie + (size_t)IE_LIST * TE;
+    V.TP = A.total_poses, V.TM = A.total_points, V.TE = A.total_edges;
+    V.edge_pose = epose, V.edge_point = epoint;
+    V.cam = A.cam + 5 * po, V.obs = A.obs + 3 * eo, V.inv_sigma2 = A.inv_sigma2 + eo;
+    auto level0 = [&EI](int e) { return !EI(IE_LEVEL, e); };  // initializeOptimization(0)'s edges
 
     // ---------------------------------------------------------------- estimates and structure
     for (int p = tid; p < P; p += T) {  // Converter::toSE3Quat
-        const float* Tp = A.Tcw + 12 * (po + p);
-        double R[9], q[4];
-        for (int r = 0; r < 3; ++r)
-            for (int col = 0; col < 3; ++col) R[3 * r + col] = (double)Tp[4 * r + col];
-        lm::quat_from_R(R, q);
-        quat_normalize(q);
-        for (int k = 0; k < 4; ++k) PD(P_EST + k, p) = q[k];
-        for (int r = 0; r < 3; ++r) PD(P_EST + 4 + r, p) = (double)Tp[4 * r + 3];
-        PI(IP_COUNT, p) = 0;
+        double q[4], t[3];
+        orbgpu::se3::pose_from_T12(A.Tcw + 12 * (po + p), q, t);
+        for (int k = 0; k < 4; ++k) V.PD(P_EST + k, p) = q[k];
+        for (int r = 0; r < 3; ++r) V.PD(P_EST + 4 + r, p) = t[r];
+        V.PI(IP_COUNT, p) = 0;
     }
     for (int m = tid; m < M; m += T) {
-        for (int k = 0; k < 3; ++k) LD(L_EST + k, m) = (double)A.Xw[3 * (lo + m) + k];
-        LI(IL_FIRST, m) = 0, LI(IL_END, m) = 0;
+        for (int k = 0; k < 3; ++k) V.LD(L_EST + k, m) = (double)A.Xw[3 * (lo + m) + k];
+        V.LI(IL_FIRST, m) = 0, V.LI(IL_END, m) = 0;
     }
     __syncthreads();
     for (int i = tid; i < E; i += T) {  // a point's run of edges
         const int m = epoint[i];
-        if (i == 0 || epoint[i - 1] != m) LI(IL_FIRST, m) = i;
-        if (i == E - 1 || epoint[i + 1] != m) LI(IL_END, m) = i + 1;
+        if (i == 0 || epoint[i - 1] != m) V.LI(IL_FIRST, m) = i;
+        if (i == E - 1 || epoint[i + 1] != m) V.LI(IL_END, m) = i + 1;
         EI(IE_LEVEL, i) = 0;
-        ED(E_CHI, i) = 0.0;
+        V.ED(E_CHI, i) = 0.0;
     }
     for (int p = tid; p < P; p += T) {  // the pose-major edge list: count, scan, fill (ascending edges)
         int n = 0;
         for (int i = 0; i < E; ++i) n += epose[i] == p;
-        PI(IP_COUNT, p) = n;
+        V.PI(IP_COUNT, p) = n;
     }
     __syncthreads();
     if (tid == 0) {
         int s = 0;
-        for (int p = 0; p < P; ++p) PI(IP_START, p) = s, s += PI(IP_COUNT, p);
+        for (int p = 0; p < P; ++p) V.PI(IP_START, p) = s, s += V.PI(IP_COUNT, p);
     }
     __syncthreads();
     for (int p = tid; p < P; p += T) {
-        int k = PI(IP_START, p);
+        int k = V.PI(IP_START, p);
         for (int i = 0; i < E; ++i)
             if (epose[i] == p) EI(IE_LIST, k++) = i;
     }
     __syncthreads();
 
-    // computeError of edge i at the estimates in field est_p / est_l: chi2, camera-frame point
-    auto edge_error = [&](int i, int est_p, int est_l, double& x, double& y, double& z, double (&e)[3],
-                          double (&q)[4], double& w, bool& stereo, const float*& cam) {
-        const int p = epose[i], m = epoint[i];
-        double t[3];
-        for (int k = 0; k < 4; ++k) q[k] = PD(est_p + k, p);
-        for (int k = 0; k < 3; ++k) t[k] = PD(est_p + 4 + k, p);
-        double r0, r1, r2;
-        lm::quat_rotate(q, LD(est_l, m), LD(est_l + 1, m), LD(est_l + 2, m), r0, r1, r2);
-        x = r0 + t[0], y = r1 + t[1], z = r2 + t[2];
-        cam = A.cam + 5 * (po + p);
-        const double fx = (double)cam[0], fy = (double)cam[1], cx = (double)cam[2], cy = (double)cam[3];
-        const float* ob = A.obs + 3 * (eo + i);
-        w = (double)A.inv_sigma2[eo + i];
-        stereo = ob[2] >= 0.0f;
-        if (stereo) {
-            const double bf = (double)cam[4];
-            const double invzf = (double)(float)(1.0 / z);  // const float invz = 1.0f / trans_xyz[2]
-            const double us = (x * invzf) * fx + cx;
-            const double vs = (y * invzf) * fy + cy;
-            const double rs = us - bf * invzf;
-            e[0] = (double)ob[0] - us;
-            e[1] = (double)ob[1] - vs;
-            e[2] = (double)ob[2] - rs;
-            return (e[0] * (w * e[0]) + e[1] * (w * e[1])) + e[2] * (w * e[2]);
-        }
-        e[0] = (double)ob[0] - ((x / z) * fx + cx);
-        e[1] = (double)ob[1] - ((y / z) * fy + cy);
-        e[2] = 0.0;
-        return e[0] * (w * e[0]) + e[1] * (w * e[1]);
-    };
-
-    // computeActiveErrors (+ linearizeOplus and the per-edge terms of buildSystem when `build`) at
-    // est / trial; returns the robust chi2 over the active edges
-    auto evaluate = [&](bool at_trial, bool build, bool robust) {
-        const int est_p = at_trial ? P_TRIAL : P_EST, est_l = at_trial ? L_TRIAL : L_EST;
+    // computeActiveErrors at the trial, or at the estimates with linearizeOplus and the per-edge
+    // terms of buildSystem (`build`); returns the robust chi2 over the active edges
+    auto evaluate = [&](bool build, bool robust) {
         double acc = 0.0;
         for (int i = tid; i < E; i += T) {
             if (EI(IE_LEVEL, i)) continue;
-            double x, y, z, e[3], q[4], w;
-            bool stereo;
-            const float* cam;
-            const double chi2 = edge_error(i, est_p, est_l, x, y, z, e, q, w, stereo, cam);
-            ED(E_CHI, i) = chi2;
-            double rho0 = chi2, rho1 = 1.0;
-            if (robust)
-                lm::huber(chi2, stereo ? A.delta_stereo : A.delta_mono, stereo ? A.dsqr_stereo : A.dsqr_mono, rho0,
-                          rho1);
-            acc += rho0;
-            if (!build) continue;
-            const double fx = (double)cam[0], fy = (double)cam[1], bf = (double)cam[4];
-            double R[3][3], Jl[3][3], Jp[3][6];
-            quat_to_R(q, R);
-            const double z_2 = z * z;
-            if (stereo) {
-                for (int col = 0; col < 3; ++col) {
-                    Jl[0][col] = ((-fx) * R[0][col]) / z + ((fx * x) * R[2][col]) / z_2;
-                    Jl[1][col] = ((-fy) * R[1][col]) / z + ((fy * y) * R[2][col]) / z_2;
-                    Jl[2][col] = Jl[0][col] - (bf * R[2][col]) / z_2;
-                }
-            } else {  // -1./z * tmp * R
-                const double s = -1.0 / z;
-                const double t00 = s * fx, t01 = s * 0.0, t02 = s * (((-x) / z) * fx);
-                const double t10 = s * 0.0, t11 = s * fy, t12 = s * (((-y) / z) * fy);
-                for (int col = 0; col < 3; ++col) {
-                    Jl[0][col] = (t00 * R[0][col] + t01 * R[1][col]) + t02 * R[2][col];
-                    Jl[1][col] = (t10 * R[0][col] + t11 * R[1][col]) + t12 * R[2][col];
-                    Jl[2][col] = 0.0;
-                }
-            }
-            Jp[0][0] = ((x * y) / z_2) * fx;
-            Jp[0][1] = (-(1.0 + (x * x) / z_2)) * fx;
-            Jp[0][2] = (y / z) * fx;
-            Jp[0][3] = (-1.0 / z) * fx;
-            Jp[0][4] = 0.0;
-            Jp[0][5] = (x / z_2) * fx;
-            Jp[1][0] = (1.0 + (y * y) / z_2) * fy;
-            Jp[1][1] = (((-x) * y) / z_2) * fy;
-            Jp[1][2] = ((-x) / z) * fy;
-            Jp[1][3] = 0.0;
-            Jp[1][4] = (-1.0 / z) * fy;
-            Jp[1][5] = (y / z_2) * fy;
-            if (stereo) {
-                Jp[2][0] = Jp[0][0] - (bf * y) / z_2;
-                Jp[2][1] = Jp[0][1] + (bf * x) / z_2;
-                Jp[2][2] = Jp[0][2];
-                Jp[2][3] = Jp[0][3];
-                Jp[2][4] = 0.0;
-                Jp[2][5] = Jp[0][5] - bf / z_2;
-            } else {
-                for (int k = 0; k < 6; ++k) Jp[2][k] = 0.0;
-            }
-            const double Wt = rho1 * w;
-            ED(E_W, i) = Wt;
-            for (int r = 0; r < 3; ++r) {
-                ED(E_OMR + r, i) = rho1 * (-(w * e[r]));
-                for (int k = 0; k < 6; ++k) ED(E_JP + 6 * r + k, i) = Jp[r][k];
-                for (int k = 0; k < 3; ++k) ED(E_JL + 3 * r + k, i) = Jl[r][k];
-            }
-            for (int a = 0; a < 6; ++a)
-                for (int col = 0; col < 3; ++col)
-                    ED(E_B + 3 * a + col, i) = ((Wt * Jp[0][a]) * Jl[0][col] + (Wt * Jp[1][a]) * Jl[1][col]) +
-                                               (Wt * Jp[2][a]) * Jl[2][col];
+            double chi2;
+            acc += build ? ba::edge_build(V, i, P_EST, L_EST, robust, A.hc, chi2)
+                         : ba::edge_chi(V, i, P_TRIAL, L_TRIAL, robust, A.hc, chi2);
+            V.ED(E_CHI, i) = chi2;
         }
-        return block_total(acc, s_val, s_row, c);
+        return job_total(acc, s_val, s_row, c);
     };
 
     // the diagonal blocks and right-hand sides of buildSystem: one lane per entry
     auto build_blocks = [&] {
+        bool diagonal;
         for (int wi = tid; wi < P * 27; wi += T) {
             const int p = wi / 27, v = wi % 27;
-            if (!PI(IP_FREE, p)) continue;
-            const int start = PI(IP_START, p), count = PI(IP_COUNT, p);
-            double acc = 0.0;
-            if (v < 21) {
-                int j, k;
-                upper_jk<6>(v, j, k);
-                for (int s = 0; s < count; ++s) {
-                    const int e = EI(IE_LIST, start + s);
-                    if (EI(IE_LEVEL, e)) continue;
-                    const double Wt = ED(E_W, e);
-                    acc += ((Wt * ED(E_JP + j, e)) * ED(E_JP + k, e) + (Wt * ED(E_JP + 6 + j, e)) * ED(E_JP + 6 + k, e)) +
-                           (Wt * ED(E_JP + 12 + j, e)) * ED(E_JP + 12 + k, e);
-                }
-            } else {
-                const int j = v - 21;
-                for (int s = 0; s < count; ++s) {
-                    const int e = EI(IE_LIST, start + s);
-                    if (EI(IE_LEVEL, e)) continue;
-                    acc += (ED(E_JP + j, e) * ED(E_OMR, e) + ED(E_JP + 6 + j, e) * ED(E_OMR + 1, e)) +
-                           ED(E_JP + 12 + j, e) * ED(E_OMR + 2, e);
-                }
-            }
-            PD(P_H + v, p) = acc;
+            if (V.PI(IP_FREE, p)) V.PD(P_H + v, p) = ba::pose_entry(V, p, v, level0, diagonal);
         }
         for (int wi = tid; wi < M * 9; wi += T) {
             const int m = wi / 9, v = wi % 9;
-            if (!LI(IL_ACTIVE, m)) continue;
-            const int first = LI(IL_FIRST, m), end = LI(IL_END, m);
-            double acc = 0.0;
-            if (v < 6) {
-                int j, k;
-                upper_jk<3>(v, j, k);
-                for (int e = first; e < end; ++e) {
-                    if (EI(IE_LEVEL, e)) continue;
-                    const double Wt = ED(E_W, e);
-                    acc += ((Wt * ED(E_JL + j, e)) * ED(E_JL + k, e) + (Wt * ED(E_JL + 3 + j, e)) * ED(E_JL + 3 + k, e)) +
-                           (Wt * ED(E_JL + 6 + j, e)) * ED(E_JL + 6 + k, e);
-                }
-            } else {
-                const int j = v - 6;
-                for (int e = first; e < end; ++e) {
-                    if (EI(IE_LEVEL, e)) continue;
-                    acc += (ED(E_JL + j, e) * ED(E_OMR, e) + ED(E_JL + 3 + j, e) * ED(E_OMR + 1, e)) +
-                           ED(E_JL + 6 + j, e) * ED(E_OMR + 2, e);
-                }
-            }
-            LD(L_H + v, m) = acc;
+            if (V.LI(IL_ACTIVE, m)) V.LD(L_H + v, m) = ba::point_entry(V, m, v, level0, diagonal);
         }
         __syncthreads();
-    };
-
-    // Dinv (row-major, symmetric) of point m from its six stored entries
-    auto load_dinv = [&](int m, double (&D)[3][3]) {
-        D[0][0] = LD(L_DINV, m), D[0][1] = LD(L_DINV + 1, m), D[0][2] = LD(L_DINV + 2, m);
-        D[1][1] = LD(L_DINV + 3, m), D[1][2] = LD(L_DINV + 4, m), D[2][2] = LD(L_DINV + 5, m);
-        D[1][0] = D[0][1], D[2][0] = D[0][2], D[2][1] = D[1][2];
     };
 
     // BlockSolver::solve at lambda: x of the free poses in v_x, of the active points in L_X; leaves
@@ -478,31 +267,11 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
     auto solve = [&](double lambda) {
         const int nf = c.nf;
         const int n = 6 * nf;
-        for (int m = tid; m < M; m += T) {  // Dinv = (Hll + lambda I)^-1 from cofactors, Dinv b_l
-            if (!LI(IL_ACTIVE, m)) continue;
-            const double a = LD(L_H, m) + lambda, b = LD(L_H + 1, m), cc = LD(L_H + 2, m);
-            const double d = LD(L_H + 3, m) + lambda, e = LD(L_H + 4, m), f = LD(L_H + 5, m) + lambda;
-            const double c00 = d * f - e * e, c01 = cc * e - b * f, c02 = b * e - cc * d;
-            const double c11 = a * f - cc * cc, c12 = b * cc - a * e, c22 = a * d - b * b;
-            const double inv = 1.0 / ((a * c00 + b * c01) + cc * c02);
-            const double D[3][3] = {{c00 * inv, c01 * inv, c02 * inv},
-                                    {c01 * inv, c11 * inv, c12 * inv},
-                                    {c02 * inv, c12 * inv, c22 * inv}};
-            LD(L_DINV, m) = D[0][0], LD(L_DINV + 1, m) = D[0][1], LD(L_DINV + 2, m) = D[0][2];
-            LD(L_DINV + 3, m) = D[1][1], LD(L_DINV + 4, m) = D[1][2], LD(L_DINV + 5, m) = D[2][2];
-            const double b0 = LD(L_H + 6, m), b1 = LD(L_H + 7, m), b2 = LD(L_H + 8, m);
-            for (int k = 0; k < 3; ++k) LD(L_V + k, m) = (D[k][0] * b0 + D[k][1] * b1) + D[k][2] * b2;
-        }
+        for (int m = tid; m < M; m += T)  // Dinv = (Hll + lambda I)^-1, Dinv b_l
+            if (V.LI(IL_ACTIVE, m)) ba::point_inverse(V, m, lambda);
         __syncthreads();
-        for (int i = tid; i < E; i += T) {  // B Dinv of every edge that has a B
-            if (EI(IE_LEVEL, i) || !PI(IP_FREE, epose[i])) continue;
-            double D[3][3];
-            load_dinv(epoint[i], D);
-            for (int a = 0; a < 6; ++a) {
-                const double b0 = ED(E_B + 3 * a, i), b1 = ED(E_B + 3 * a + 1, i), b2 = ED(E_B + 3 * a + 2, i);
-                for (int k = 0; k < 3; ++k) ED(E_BD + 3 * a + k, i) = (b0 * D[0][k] + b1 * D[1][k]) + b2 * D[2][k];
-            }
-        }
+        for (int i = tid; i < E; i += T)  // B Dinv of every edge that has a B
+            if (!EI(IE_LEVEL, i) && V.PI(IP_FREE, epose[i])) ba::edge_bd(V, i);
         __syncthreads();
         // S = Hpp + lambda I - sum (B Dinv) B^T, upper block triangle.  Half a row of S -- columns
         // s0..s0+2 of every block (a, b >= a) in row r of pose a -- has one owner, which walks the edges
@@ -512,48 +281,35 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
         // iteration at 20 free poses and 12,000 edges)
         for (int wi = tid; wi < nf * 12; wi += T) {
             const int ia = wi / 12, r = (wi % 12) >> 1, s0 = 3 * (wi & 1);
-            const int pa = PI(IP_HLIST, ia);
+            const int pa = V.PI(IP_HLIST, ia);
             double* const row = S + (size_t)(6 * ia + r) * n;
             for (int ib = ia; ib < nf; ++ib)
                 for (int s = s0; s < s0 + 3; ++s) {
                     double h = 0.0;
                     if (ib == ia && s >= r) {
-                        h = PD(P_H + lm::upper_index<6>(r, s), pa);
+                        h = V.PD(P_H + lm::upper_index<6>(r, s), pa);
                         if (s == r) h = h + lambda;
                     }
                     row[6 * ib + s] = h;
                 }
-            const int start = PI(IP_START, pa), count = PI(IP_COUNT, pa);
+            const int start = V.PI(IP_START, pa), count = V.PI(IP_COUNT, pa);
             for (int k = 0; k < count; ++k) {
                 const int e = EI(IE_LIST, start + k);
                 if (EI(IE_LEVEL, e)) continue;
                 const int m = epoint[e];
-                const double d0 = ED(E_BD + 3 * r, e), d1 = ED(E_BD + 3 * r + 1, e), d2 = ED(E_BD + 3 * r + 2, e);
-                const int end = LI(IL_END, m);
-                for (int e2 = LI(IL_FIRST, m); e2 < end; ++e2) {
+                const double d0 = V.ED(E_BD + 3 * r, e), d1 = V.ED(E_BD + 3 * r + 1, e), d2 = V.ED(E_BD + 3 * r + 2, e);
+                const int end = V.LI(IL_END, m);
+                for (int e2 = V.LI(IL_FIRST, m); e2 < end; ++e2) {
                     const int p2 = epose[e2];
-                    if (EI(IE_LEVEL, e2) || !PI(IP_FREE, p2)) continue;
-                    const int ib = PI(IP_HIDX, p2);
+                    if (EI(IE_LEVEL, e2) || !V.PI(IP_FREE, p2)) continue;
+                    const int ib = V.PI(IP_HIDX, p2);
                     if (ib < ia) continue;
                     for (int s = s0; s < s0 + 3; ++s)
-                        row[6 * ib + s] -= (d0 * ED(E_B + 3 * s, e2) + d1 * ED(E_B + 3 * s + 1, e2)) + d2 * ED(E_B + 3 * s + 2, e2);
+                        row[6 * ib + s] -= (d0 * V.ED(E_B + 3 * s, e2) + d1 * V.ED(E_B + 3 * s + 1, e2)) + d2 * V.ED(E_B + 3 * s + 2, e2);
                 }
             }
         }
-        for (int wi = tid; wi < n; wi += T) {  // b_schur = b_p - sum B (Dinv b_l)
-            const int ia = wi / 6, j = wi % 6;
-            const int pa = PI(IP_HLIST, ia);
-            const int start = PI(IP_START, pa), count = PI(IP_COUNT, pa);
-            double coef = 0.0;
-            for (int k = 0; k < count; ++k) {
-                const int e = EI(IE_LIST, start + k);
-                if (EI(IE_LEVEL, e)) continue;
-                const int m = epoint[e];
-                coef += (ED(E_B + 3 * j, e) * LD(L_V, m) + ED(E_B + 3 * j + 1, e) * LD(L_V + 1, m)) +
-                        ED(E_B + 3 * j + 2, e) * LD(L_V + 2, m);
-            }
-            v_s[wi] = PD(P_H + 21 + j, pa) - coef;
-        }
+        for (int wi = tid; wi < n; wi += T) v_s[wi] = ba::b_schur_entry(V, wi / 6, wi % 6, level0);
         __syncthreads();
         // Cholesky, column by column: A in the upper triangle of S, L below it, its diagonal in v_d
         int ok = 1;
@@ -593,53 +349,17 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
         }
         if (tid == 0) c.solved = ok;
         __syncthreads();
-        for (int m = tid; m < M; m += T) {  // x_l = Dinv (b_l - B^T x_p)
-            if (!LI(IL_ACTIVE, m)) continue;
-            double t[3] = {LD(L_H + 6, m), LD(L_H + 7, m), LD(L_H + 8, m)};
-            if (ok) {
-                const int end = LI(IL_END, m);
-                for (int e = LI(IL_FIRST, m); e < end; ++e) {
-                    const int p = epose[e];
-                    if (EI(IE_LEVEL, e) || !PI(IP_FREE, p)) continue;
-                    const double* xp = v_x + 6 * PI(IP_HIDX, p);
-                    for (int k = 0; k < 3; ++k) {
-                        double dot = ED(E_B + k, e) * xp[0];
-                        for (int a = 1; a < 6; ++a) dot = dot + ED(E_B + 3 * a + k, e) * xp[a];
-                        t[k] -= dot;
-                    }
-                }
-                double D[3][3];
-                load_dinv(m, D);
-                for (int k = 0; k < 3; ++k) LD(L_X + k, m) = (D[k][0] * t[0] + D[k][1] * t[1]) + D[k][2] * t[2];
-            } else {
-                for (int k = 0; k < 3; ++k) LD(L_X + k, m) = 0.0;
-            }
-        }
+        for (int m = tid; m < M; m += T)  // x_l = Dinv (b_l - B^T x_p)
+            if (V.LI(IL_ACTIVE, m)) ba::point_x(V, m, v_x, ok != 0, level0);
         __syncthreads();
     };
 
     // trial = oplus(x) on est: exp(x) * estimate for a free pose, estimate + x for an active point
     auto make_trial = [&] {
         const bool ok = c.solved != 0;
-        for (int p = tid; p < P; p += T) {
-            double q[4], t[3];
-            for (int k = 0; k < 4; ++k) q[k] = PD(P_EST + k, p);
-            for (int k = 0; k < 3; ++k) t[k] = PD(P_EST + 4 + k, p);
-            if (ok && PI(IP_FREE, p)) {
-                const double* xp = v_x + 6 * PI(IP_HIDX, p);
-                const double x[6] = {xp[0], xp[1], xp[2], xp[3], xp[4], xp[5]};
-                double oq[4], ot[3];
-                se3_exp_times(q, t, x, oq, ot);
-                for (int k = 0; k < 4; ++k) q[k] = oq[k];
-                for (int k = 0; k < 3; ++k) t[k] = ot[k];
-            }
-            for (int k = 0; k < 4; ++k) PD(P_TRIAL + k, p) = q[k];
-            for (int k = 0; k < 3; ++k) PD(P_TRIAL + 4 + k, p) = t[k];
-        }
-        for (int m = tid; m < M; m += T) {
-            const bool moved = ok && LI(IL_ACTIVE, m);
-            for (int k = 0; k < 3; ++k) LD(L_TRIAL + k, m) = moved ? LD(L_EST + k, m) + LD(L_X + k, m) : LD(L_EST + k, m);
-        }
+        for (int p = tid; p < P; p += T)
+            ba::pose_oplus(V, p, ok && V.PI(IP_FREE, p) ? v_x + 6 * V.PI(IP_HIDX, p) : nullptr);
+        for (int m = tid; m < M; m += T) ba::point_oplus(V, m, ok && V.LI(IL_ACTIVE, m));
         __syncthreads();
     };
 
@@ -649,15 +369,15 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
         const int n = 6 * c.nf;
         for (int wi = tid; wi < n; wi += T) {
             const double x = v_x[wi];
-            acc += x * (lambda * x + PD(P_H + 21 + wi % 6, PI(IP_HLIST, wi / 6)));
+            acc += x * (lambda * x + V.PD(P_H + 21 + wi % 6, V.PI(IP_HLIST, wi / 6)));
         }
         for (int wi = tid; wi < 3 * M; wi += T) {
             const int m = wi / 3, k = wi % 3;
-            if (!LI(IL_ACTIVE, m)) continue;
-            const double x = LD(L_X + k, m);
-            acc += x * (lambda * x + LD(L_H + 6 + k, m));
+            if (!V.LI(IL_ACTIVE, m)) continue;
+            const double x = V.LD(L_X + k, m);
+            acc += x * (lambda * x + V.LD(L_H + 6 + k, m));
         }
-        return block_total(acc, s_val, s_row, c);
+        return job_total(acc, s_val, s_row, c);
     };
 
     int lm_iterations[2] = {0, 0}, lm_rejected[2] = {0, 0}, n_flag[2] = {0, 0};  // lane 0's
@@ -667,24 +387,24 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
         // initializeOptimization(0): what a level-0 edge touches
         for (int m = tid; m < M; m += T) {
             int act = 0;
-            const int end = LI(IL_END, m);
-            for (int e = LI(IL_FIRST, m); e < end; ++e) act |= !EI(IE_LEVEL, e);
-            LI(IL_ACTIVE, m) = act;
+            const int end = V.LI(IL_END, m);
+            for (int e = V.LI(IL_FIRST, m); e < end; ++e) act |= !EI(IE_LEVEL, e);
+            V.LI(IL_ACTIVE, m) = act;
         }
         for (int p = tid; p < P; p += T) {
             int act = 0;
-            const int start = PI(IP_START, p), count = PI(IP_COUNT, p);
+            const int start = V.PI(IP_START, p), count = V.PI(IP_COUNT, p);
             for (int k = 0; k < count; ++k) act |= !EI(IE_LEVEL, EI(IE_LIST, start + k));
-            PI(IP_FREE, p) = act && p < NL && !A.fixed[po + p];
+            V.PI(IP_FREE, p) = act && p < NL && !A.fixed[po + p];
         }
         __syncthreads();
         if (tid == 0) {
             int nf = 0, na = 0;
             for (int p = 0; p < P; ++p) {
-                PI(IP_HIDX, p) = -1;
-                if (PI(IP_FREE, p)) PI(IP_HIDX, p) = nf, PI(IP_HLIST, nf) = p, ++nf;
+                V.PI(IP_HIDX, p) = -1;
+                if (V.PI(IP_FREE, p)) V.PI(IP_HIDX, p) = nf, V.PI(IP_HLIST, nf) = p, ++nf;
             }
-            for (int m = 0; m < M; ++m) na += LI(IL_ACTIVE, m);
+            for (int m = 0; m < M; ++m) na += V.LI(IL_ACTIVE, m);
             c.nf = nf, c.n_active = na, c.done = 0, c.n_flag = 0;
             lm::run_start(c.run);
         }
@@ -693,19 +413,19 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
         if (c.nf + c.n_active > 0) {  // optimize() returns at once without an active vertex
             const int max_iter = kIterations[round];
             for (int it = 0; it < max_iter; ++it) {
-                const double chi = evaluate(false, true, robust);
+                const double chi = evaluate(true, robust);
                 build_blocks();
                 if (it == 0) {  // computeLambdaInit: the maximum is exact in any order
                     double mx = 0.0;
                     for (int wi = tid; wi < 6 * c.nf; wi += T) {
                         const int j = wi % 6;
-                        const double a = fabs(PD(P_H + lm::upper_index<6>(j, j), PI(IP_HLIST, wi / 6)));
+                        const double a = fabs(V.PD(P_H + lm::upper_index<6>(j, j), V.PI(IP_HLIST, wi / 6)));
                         mx = a < mx ? mx : a;
                     }
                     for (int wi = tid; wi < 3 * M; wi += T) {
                         const int m = wi / 3, j = wi % 3;
-                        if (!LI(IL_ACTIVE, m)) continue;
-                        const double a = fabs(LD(L_H + (j == 0 ? 0 : (j == 1 ? 3 : 5)), m));
+                        if (!V.LI(IL_ACTIVE, m)) continue;
+                        const double a = fabs(V.LD(L_H + (j == 0 ? 0 : (j == 1 ? 3 : 5)), m));
                         mx = a < mx ? mx : a;
                     }
                     s_val[tid] = mx;
@@ -722,7 +442,7 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
                     const double lambda = c.run.lambda;
                     solve(lambda);
                     make_trial();
-                    const double tmp_chi = evaluate(true, false, robust);
+                    const double tmp_chi = evaluate(false, robust);
                     const double ssum = scale_sum(lambda);
                     if (tid == 0) {
                         c.accepted = lm::run_judge(c.run, c.solved != 0, tmp_chi, ssum) ? 1 : 0;
@@ -730,8 +450,8 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
                     }
                     __syncthreads();
                     if (c.accepted) {
-                        for (int wi = tid; wi < 7 * P; wi += T) PD(P_EST + wi % 7, wi / 7) = PD(P_TRIAL + wi % 7, wi / 7);
-                        for (int wi = tid; wi < 3 * M; wi += T) LD(L_EST + wi % 3, wi / 3) = LD(L_TRIAL + wi % 3, wi / 3);
+                        for (int wi = tid; wi < 7 * P; wi += T) V.PD(P_EST + wi % 7, wi / 7) = V.PD(P_TRIAL + wi % 7, wi / 7);
+                        for (int wi = tid; wi < 3 * M; wi += T) V.LD(L_EST + wi % 3, wi / 3) = V.LD(L_TRIAL + wi % 3, wi / 3);
                     }
                     __syncthreads();
                     if (!c.more) break;
@@ -745,11 +465,9 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
         // the test of Optimizer.cpp:773-804 / :818-847: chi2() as the edge holds it, depth at the kept estimates
         int flagged = 0;
         for (int i = tid; i < E; i += T) {
-            double x, y, z, e[3], q[4], w;
-            bool stereo;
-            const float* cam;
-            (void)edge_error(i, P_EST, L_EST, x, y, z, e, q, w, stereo, cam);
-            const bool flag = ED(E_CHI, i) > (stereo ? 7.815 : 5.991) || !(z > 0.0);
+            ba::EdgeAt g;
+            ba::edge_error(V, i, P_EST, L_EST, g);
+            const bool flag = V.ED(E_CHI, i) > (g.stereo ? 7.815 : 5.991) || !(g.z > 0.0);
             if (round == 0)
                 EI(IE_LEVEL, i) = flag ? 1 : 0;
             else
@@ -767,21 +485,15 @@ __global__ __launch_bounds__(kThreads) void localba_kernel(Args A) {
     }
 
     for (int p = tid; p < NL; p += T) {  // Converter::toCvMat(SE3Quat) of every local pose
-        const double q[4] = {PD(P_EST, p), PD(P_EST + 1, p), PD(P_EST + 2, p), PD(P_EST + 3, p)};
-        const double t[3] = {PD(P_EST + 4, p), PD(P_EST + 5, p), PD(P_EST + 6, p)};
+        const double q[4] = {V.PD(P_EST, p), V.PD(P_EST + 1, p), V.PD(P_EST + 2, p), V.PD(P_EST + 3, p)};
+        const double t[3] = {V.PD(P_EST + 4, p), V.PD(P_EST + 5, p), V.PD(P_EST + 6, p)};
         lm::write_T16(q, t, 1.0, A.Tcw_out + 16 * ((size_t)c.oo + p));
     }
-    for (int wi = tid; wi < 3 * M; wi += T) A.Xw_out[3 * lo + wi] = (float)LD(L_EST + wi % 3, wi / 3);
+    for (int wi = tid; wi < 3 * M; wi += T) A.Xw_out[3 * lo + wi] = (float)V.LD(L_EST + wi % 3, wi / 3);
     if (tid == 0) {
         res->rounds = rounds, res->n_bad_first = n_flag[0], res->n_erase = n_flag[1], res->pad = 0;
         for (int k = 0; k < 2; ++k) res->lm_iterations[k] = lm_iterations[k], res->lm_rejected[k] = lm_rejected[k];
     }
-#undef PD
-#undef LD
-#undef ED
-#undef PI
-#undef LI
-#undef EI
 }
 
 int check_args(int batch, int total_poses, int total_local, int total_points, int total_edges, int max_local,
@@ -822,7 +534,6 @@ extern "C" int orbgpu_local_ba_batch_device(int batch, const orbgpu_localba_job*
         return orbgpu::fail(ORBGPU_ERR_ARG, "null, misaligned or too small workspace");
     if (int rc = orbgpu::check_device()) return rc;
     (void)hipGetLastError();
-    const float dm = (float)std::sqrt(5.991), ds = (float)std::sqrt(7.815);  // Optimizer.cpp:666-667
     Args a;
     a.jobs = d_jobs, a.batch = batch, a.total_poses = total_poses, a.total_local = total_local;
     a.total_points = total_points, a.total_edges = total_edges, a.max_local = max_local;
@@ -830,9 +541,7 @@ extern "C" int orbgpu_local_ba_batch_device(int batch, const orbgpu_localba_job*
     a.edge_pose = d_edge_pose, a.edge_point = d_edge_point;
     a.Tcw_out = d_Tcw_out, a.Xw_out = d_Xw_out, a.erase = d_erase, a.results = d_results;
     a.ws = static_cast<double*>(d_workspace);
-    // robust_kernel_impl.h:85: float dsqr = delta * delta (delta a double)
-    a.delta_mono = (double)dm, a.delta_stereo = (double)ds;
-    a.dsqr_mono = (double)(float)((double)dm * (double)dm), a.dsqr_stereo = (double)(float)((double)ds * (double)ds);
+    a.hc = orbgpu::proj_edge::huber_constants(5.991, 7.815);  // Optimizer.cpp:666-667
     hipLaunchKernelGGL(localba_kernel, dim3(batch), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
     ORB_HIP(hipGetLastError());
     return ORBGPU_OK;

@@ -8,8 +8,12 @@
 // tests/poseopt_ref.py is the same arithmetic, expression for expression.
 // The LM state machine, the 6x6 solve, Huber, the quaternion algebra, the
 // workgroup sum and the matrix write-out are lm_device.h's, shared with
-// sim3opt.hip; this file adds SE3Quat's exp(x) * estimate, the two edges and
-// the four rounds with their classification.
+// sim3opt.hip; the Huber thresholds are projection_edge.h's.  This file adds
+// SE3Quat's exp(x) * estimate, the two OnlyPose edges and the four rounds with
+// their classification.  Its SE3Quat and computeError are the text of
+// se3_device.h and projection_edge.h: calling those instead compiled this
+// kernel to other code, which measured up to 2 % slower at 300 edges a job for
+// a reason that was not found, so the kernel keeps its own.
 //
 // One workgroup per job, one launch for the whole optimisation.  Edge i of a
 // job belongs to lane i % T for the whole call: the lane reads it (from LDS
@@ -38,6 +42,7 @@
 #include "host_common.h"
 #include "host_ctx.h"
 #include "lm_device.h"
+#include "projection_edge.h"
 
 namespace {
 
@@ -61,10 +66,7 @@ constexpr int kVals = Lm::kVals;  // H (21), b (6), robust chi2
 constexpr int kIterations = 10;   // optimizer.optimize(its[it]), Optimizer.cpp:441
 constexpr int kMaxPasses = 1 + kIterations * lm::kMaxTrials;
 
-// (float)sqrt(5.991), (float)sqrt(7.815) and their float squares (Huber's dsqr), from the host
-struct HuberConst {
-    double delta_mono, delta_stereo, dsqr_mono, dsqr_stereo;
-};
+using orbgpu::proj_edge::HuberConst;
 
 // the job's state in LDS; written by lane 0 between barriers, read by all
 struct Ctl {
@@ -378,12 +380,6 @@ __global__ __launch_bounds__(T) void poseopt_kernel(const orbgpu_poseopt_job* __
     }
 }
 
-HuberConst huber_constants() {
-    const float dm = (float)std::sqrt(5.991), ds = (float)std::sqrt(7.815);  // Optimizer.cpp:331-332
-    // robust_kernel_impl.h:85: float dsqr = delta * delta (delta a double)
-    return {(double)dm, (double)ds, (double)(float)((double)dm * (double)dm), (double)(float)((double)ds * (double)ds)};
-}
-
 }  // namespace
 
 extern "C" int orbgpu_pose_optimization_batch_device(int batch, const orbgpu_poseopt_job* d_jobs, int total_obs,
@@ -397,7 +393,7 @@ extern "C" int orbgpu_pose_optimization_batch_device(int batch, const orbgpu_pos
     if (int rc = orbgpu::check_device()) return rc;
     (void)hipGetLastError();
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const HuberConst hc = huber_constants();
+    const HuberConst hc = orbgpu::proj_edge::huber_constants(5.991, 7.815);  // Optimizer.cpp:331-332
     hipLaunchKernelGGL(poseopt_kernel<kThreads>, dim3(batch), dim3(kThreads), 0, s, d_jobs, total_obs, d_Xw, d_obs,
                        d_inv_sigma2, d_results, d_outlier, hc);
     ORB_HIP(hipGetLastError());

@@ -8,22 +8,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include "se3_device.h"
 #include "sim3opt_device.h"
 
 namespace orbgpu {
 namespace sim3opt {
 
-// Eigen's Quaternion::toRotationMatrix of q = (x, y, z, w), not normalised
-__device__ inline void quat_to_R(const double (&q)[4], double (&R)[3][3]) {
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0][0] = 1.0 - (tyy + tzz), R[0][1] = txy - twz, R[0][2] = txz + twy;
-    R[1][0] = txy + twz, R[1][1] = 1.0 - (txx + tzz), R[1][2] = tyz - twx;
-    R[2][0] = txz - twy, R[2][1] = tyz + twx, R[2][2] = 1.0 - (txx + tyy);
-}
+using se3::quat_to_R;  // Eigen's Quaternion::toRotationMatrix of q = (x, y, z, w), not normalised
 
 // W x = t by elimination with partial pivoting, the first largest |entry| of the column; the
 // order is tests/essential_ref.py's (Eigen's W.lu().solve(t) is restated, not reproduced)
