@@ -4,8 +4,9 @@
 // include/orbgpu_localba.h.  Header-only; link liborbgpu.so.
 //
 //   void ORB_SLAM2::LocalBundleAdjustmentGPU(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int device = -1)
+//   void ORB_SLAM2::LocalBundleAdjustmentChipGPU(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, int device = -1)
 //
-// does what the reference's function does to its arguments: the gather of
+// The first does what the reference's function does to its arguments: the gather of
 // :540-752 in the reference's order with its mnBALocalForKF / mnBAFixedForKF
 // bookkeeping (local keyframes: pKF, then its covisible keyframes that are not
 // bad; local MapPoints: those of the local keyframes, not bad, first seen first;
@@ -15,7 +16,12 @@
 // erasures in the reference's order (monocular edges, then stereo), SetPose of
 // every local keyframe and SetWorldPos + UpdateNormalAndDepth of every local
 // MapPoint.  *pbStopFlag is read once, before the call (:754-756); g2o's
-// mid-run stop is not reproduced, and neither is a MapPoint that turns bad
+// mid-run stop is not reproduced by the first form (one asynchronous launch per
+// batch); the second, through include/orbgpu_localba_chip.h, spreads the one
+// neighbourhood over the whole chip and hands pbStopFlag to a host loop that
+// polls it where g2o does and reads it between the rounds (:764-766).  Both share
+// the gather, the erasure replay and the write-back (localba_detail).  Neither
+// reproduces a MapPoint that turns bad
 // while the optimisation runs (the reference skips its edge in the first
 // classification).  The class Optimizer is not replaced; the reference's member
 // forwards here in one line.  A template over the keyframe
@@ -41,18 +47,41 @@
 #include <vector>
 
 #include "../orbgpu_localba.h"
+#include "../orbgpu_localba_chip.h"
 #include "Device.h"
 
 namespace ORB_SLAM2 {
 
-// device (adapter-only, Device.h): the GPU the call runs on (-1: the thread's)
-template <class KeyFrameT, class MapT>
-void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int device = -1) {
+namespace localba_detail {
+
+// what the gather of :540-752 leaves: the lists, and the job's arrays in orbgpu_localba.h's layout
+template <class KeyFrameT, class MapPointT>
+struct Gathered {
+    std::list<KeyFrameT*> lLocalKeyFrames, lFixedCameras;
+    std::list<MapPointT*> lLocalMapPoints;
+    std::vector<float> Tcw, cam, Xw, obs, inv_sigma2;
+    std::vector<uint8_t> fixed;
+    std::vector<int> edge_pose, edge_point;
+    std::vector<KeyFrameT*> vpEdgeKF;
+    std::vector<MapPointT*> vpMapPointEdge;
+    int n_local() const { return (int)lLocalKeyFrames.size(); }
+    int n_poses() const { return (int)fixed.size(); }
+    int n_points() const { return (int)lLocalMapPoints.size(); }
+    int n_edges() const { return (int)edge_pose.size(); }
+};
+
+template <class KeyFrameT, class MapPointT>
+void Gather(KeyFrameT* pKF, Gathered<KeyFrameT, MapPointT>& g) {
     typedef typename std::decay<decltype(pKF->GetMapPointMatches())>::type MapPointVecT;
-    typedef typename std::remove_pointer<typename MapPointVecT::value_type>::type MapPointT;
+    std::list<KeyFrameT*>&lLocalKeyFrames = g.lLocalKeyFrames, &lFixedCameras = g.lFixedCameras;
+    std::list<MapPointT*>& lLocalMapPoints = g.lLocalMapPoints;
+    std::vector<float>&Tcw = g.Tcw, &cam = g.cam, &Xw = g.Xw, &obs = g.obs, &inv_sigma2 = g.inv_sigma2;
+    std::vector<uint8_t>& fixed = g.fixed;
+    std::vector<int>&edge_pose = g.edge_pose, &edge_point = g.edge_point;
+    std::vector<KeyFrameT*>& vpEdgeKF = g.vpEdgeKF;
+    std::vector<MapPointT*>& vpMapPointEdge = g.vpMapPointEdge;
 
     // Local KeyFrames: First Breadth Search from Current Keyframe
-    std::list<KeyFrameT*> lLocalKeyFrames;
     lLocalKeyFrames.push_back(pKF);
     pKF->mnBALocalForKF = pKF->mnId;
     const std::vector<KeyFrameT*> vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
@@ -63,7 +92,6 @@ void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int 
     }
 
     // Local MapPoints seen in Local KeyFrames
-    std::list<MapPointT*> lLocalMapPoints;
     for (typename std::list<KeyFrameT*>::iterator lit = lLocalKeyFrames.begin(); lit != lLocalKeyFrames.end(); lit++) {
         MapPointVecT vpMPs = (*lit)->GetMapPointMatches();
         for (typename MapPointVecT::iterator vit = vpMPs.begin(); vit != vpMPs.end(); vit++) {
@@ -76,7 +104,6 @@ void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int 
     }
 
     // Fixed Keyframes. Keyframes that see Local MapPoints but that are not Local Keyframes
-    std::list<KeyFrameT*> lFixedCameras;
     for (typename std::list<MapPointT*>::iterator lit = lLocalMapPoints.begin(); lit != lLocalMapPoints.end(); lit++) {
         std::map<KeyFrameT*, size_t> observations = (*lit)->GetObservations();
         for (typename std::map<KeyFrameT*, size_t>::iterator mit = observations.begin(); mit != observations.end();
@@ -91,8 +118,6 @@ void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int 
 
     // the vertices: local poses, fixed poses, points
     std::map<KeyFrameT*, int> pose_index;
-    std::vector<float> Tcw, cam;
-    std::vector<uint8_t> fixed;
     for (int pass = 0; pass < 2; ++pass) {
         std::list<KeyFrameT*>& l = pass == 0 ? lLocalKeyFrames : lFixedCameras;
         for (typename std::list<KeyFrameT*>::iterator lit = l.begin(); lit != l.end(); lit++) {
@@ -107,10 +132,6 @@ void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int 
         }
     }
     // the edges, grouped by point
-    std::vector<float> Xw, obs, inv_sigma2;
-    std::vector<int> edge_pose, edge_point;
-    std::vector<KeyFrameT*> vpEdgeKF;
-    std::vector<MapPointT*> vpMapPointEdge;
     int m = 0;
     for (typename std::list<MapPointT*>::iterator lit = lLocalMapPoints.begin(); lit != lLocalMapPoints.end();
          lit++, ++m) {
@@ -137,28 +158,18 @@ void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int 
         }
     }
 
-    if (pbStopFlag)
-        if (*pbStopFlag) return;
+}
 
-    const int n_local = (int)lLocalKeyFrames.size(), n_poses = (int)fixed.size();
-    const int n_points = (int)lLocalMapPoints.size(), n_edges = (int)edge_pose.size();
-    // no local MapPoint: nothing to optimise, and no device is needed.  (The reference would still
-    // rewrite every local pose with its quaternion round trip; that is not reproduced.)
-    if (n_points == 0) return;
-    orbgpu_localba_job job;
-    job.n_poses = n_poses, job.n_local = n_local, job.n_points = n_points, job.n_edges = n_edges;
-    job.pose_offset = 0, job.point_offset = 0, job.edge_offset = 0, job.out_pose_offset = 0;
-    std::vector<float> Tcw_out((size_t)16 * n_local), Xw_out((size_t)3 * n_points);
-    std::vector<uint8_t> erase((size_t)n_edges, 0);
-    orbgpu_localba_result r;
-    {
-        const orbslam2_amd::DeviceGuard device_guard(device);
-        if (orbgpu_local_ba_batch(1, &job, n_poses, n_local, n_points, n_edges, n_local, Tcw.data(), fixed.data(),
-                                  cam.data(), Xw.data(), edge_pose.data(), edge_point.data(), obs.data(),
-                                  inv_sigma2.data(), Tcw_out.data(), Xw_out.data(), erase.data(), &r, NULL,
-                                  0) != ORBGPU_OK)
-            throw std::runtime_error(std::string("orbgpu: ") + orbgpu_last_error());
-    }
+// the erasure replay of :779-803 / :823-847 and the write-back of :850-885 under pMap->mMutexMapUpdate
+template <class KeyFrameT, class MapPointT, class MapT>
+void WriteBack(Gathered<KeyFrameT, MapPointT>& g, MapT* pMap, const std::vector<float>& Tcw_out,
+               const std::vector<float>& Xw_out, const std::vector<uint8_t>& erase) {
+    std::list<KeyFrameT*>& lLocalKeyFrames = g.lLocalKeyFrames;
+    std::list<MapPointT*>& lLocalMapPoints = g.lLocalMapPoints;
+    const std::vector<float>& obs = g.obs;
+    const std::vector<KeyFrameT*>& vpEdgeKF = g.vpEdgeKF;
+    const std::vector<MapPointT*>& vpMapPointEdge = g.vpMapPointEdge;
+    const int n_edges = g.n_edges();
 
     // vToErase: the monocular edges in edge order, then the stereo edges
     std::vector<std::pair<KeyFrameT*, MapPointT*> > vToErase;
@@ -187,7 +198,7 @@ void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int 
         for (int e = 0; e < 16; ++e) T.template at<float>(e / 4, e % 4) = Tcw_out[(size_t)16 * k + e];
         (*lit)->SetPose(T);
     }
-    m = 0;
+    int m = 0;
     for (typename std::list<MapPointT*>::iterator lit = lLocalMapPoints.begin(); lit != lLocalMapPoints.end();
          lit++, ++m) {
         cv::Mat pos(3, 1, CV_32F);
@@ -195,6 +206,71 @@ void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int 
         (*lit)->SetWorldPos(pos);
         (*lit)->UpdateNormalAndDepth();
     }
+}
+
+
+}  // namespace localba_detail
+
+// device (adapter-only, Device.h): the GPU the call runs on (-1: the thread's)
+template <class KeyFrameT, class MapT>
+void LocalBundleAdjustmentGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int device = -1) {
+    typedef typename std::decay<decltype(pKF->GetMapPointMatches())>::type MapPointVecT;
+    typedef typename std::remove_pointer<typename MapPointVecT::value_type>::type MapPointT;
+    localba_detail::Gathered<KeyFrameT, MapPointT> g;
+    localba_detail::Gather(pKF, g);
+
+    if (pbStopFlag)
+        if (*pbStopFlag) return;
+
+    const int n_local = g.n_local(), n_poses = g.n_poses(), n_points = g.n_points(), n_edges = g.n_edges();
+    // no local MapPoint: nothing to optimise, and no device is needed.  (The reference would still
+    // rewrite every local pose with its quaternion round trip; that is not reproduced.)
+    if (n_points == 0) return;
+    orbgpu_localba_job job;
+    job.n_poses = n_poses, job.n_local = n_local, job.n_points = n_points, job.n_edges = n_edges;
+    job.pose_offset = 0, job.point_offset = 0, job.edge_offset = 0, job.out_pose_offset = 0;
+    std::vector<float> Tcw_out((size_t)16 * n_local), Xw_out((size_t)3 * n_points);
+    std::vector<uint8_t> erase((size_t)n_edges, 0);
+    orbgpu_localba_result r;
+    {
+        const orbslam2_amd::DeviceGuard device_guard(device);
+        if (orbgpu_local_ba_batch(1, &job, n_poses, n_local, n_points, n_edges, n_local, g.Tcw.data(), g.fixed.data(),
+                                  g.cam.data(), g.Xw.data(), g.edge_pose.data(), g.edge_point.data(), g.obs.data(),
+                                  g.inv_sigma2.data(), Tcw_out.data(), Xw_out.data(), erase.data(), &r, NULL,
+                                  0) != ORBGPU_OK)
+            throw std::runtime_error(std::string("orbgpu: ") + orbgpu_last_error());
+    }
+    localba_detail::WriteBack(g, pMap, Tcw_out, Xw_out, erase);
+}
+
+// The same through include/orbgpu_localba_chip.h: the neighbourhood spread over the whole chip, and
+// pbStopFlag passed through as the byte g2o's force-stop flag is, polled where g2o polls it and read
+// between the rounds (:764-766).  It returns at :754-756 when the flag is already set.
+template <class KeyFrameT, class MapT>
+void LocalBundleAdjustmentChipGPU(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int device = -1) {
+    static_assert(sizeof(bool) == 1, "the stop flag is read as one byte");
+    typedef typename std::decay<decltype(pKF->GetMapPointMatches())>::type MapPointVecT;
+    typedef typename std::remove_pointer<typename MapPointVecT::value_type>::type MapPointT;
+    localba_detail::Gathered<KeyFrameT, MapPointT> g;
+    localba_detail::Gather(pKF, g);
+
+    if (pbStopFlag)
+        if (*pbStopFlag) return;
+
+    const int n_local = g.n_local(), n_poses = g.n_poses(), n_points = g.n_points(), n_edges = g.n_edges();
+    if (n_points == 0) return;  // as above
+    std::vector<float> Tcw_out((size_t)16 * n_local), Xw_out((size_t)3 * n_points);
+    std::vector<uint8_t> erase((size_t)n_edges, 0);
+    orbgpu_localba_chip_result r;
+    {
+        const orbslam2_amd::DeviceGuard device_guard(device);
+        if (orbgpu_local_ba_chip(n_poses, n_local, n_points, n_edges, g.Tcw.data(), g.fixed.data(), g.cam.data(),
+                                 g.Xw.data(), g.edge_pose.data(), g.edge_point.data(), g.obs.data(),
+                                 g.inv_sigma2.data(), 5, 10, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), -1,
+                                 Tcw_out.data(), Xw_out.data(), erase.data(), &r, NULL, 0) != ORBGPU_OK)
+            throw std::runtime_error(std::string("orbgpu: ") + orbgpu_last_error());
+    }
+    localba_detail::WriteBack(g, pMap, Tcw_out, Xw_out, erase);
 }
 
 }  // namespace ORB_SLAM2

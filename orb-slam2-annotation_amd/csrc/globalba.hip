@@ -12,9 +12,11 @@
 // block, the host record, the ordered sums and the bodies of the begin and
 // judge kernels are wholechip_lm.h's, shared with essential.hip; the pose
 // write-out is lm_device.h's, the LM decisions are lm_runtime.h's.  The
-// kernels keep their own bodies over this file's Args: the per-item arithmetic
-// is ba_schur_device.h's text, and moving the kernels onto its view measured
-// 0.5-0.9 % slower in ba_schur for a reason that was not found.
+// kernels are ba_phases.h's, instantiated here over Args (no levels);
+// localba_chip.hip instantiates them with LocalBA's levels.  They keep their
+// own bodies over Args: the per-item arithmetic is ba_schur_device.h's text,
+// and moving the kernels onto its view measured 0.5-0.9 % slower in ba_schur
+// (§5q found what changes that kernel's code).
 //
 // The calling thread drives the loop.  A phase that needs the previous one
 // complete is the next launch on the stream; no kernel synchronises with
@@ -56,38 +58,16 @@
 #include <string>
 
 #include "../../include/orbgpu_globalba.h"
-#include "ba_schur_device.h"
+#include "ba_phases.h"
 #include "chol_blocked.h"
 #include "host_common.h"
 #include "host_ctx.h"
-#include "wholechip_lm.h"
 
 namespace {
 
-namespace lm = orbgpu::lm;
-namespace wc = orbgpu::wholechip;
-using namespace orbgpu::ba;  // the field offsets
-using lm::upper_jk;
-using orbgpu::se3::quat_to_R;
-using orbgpu::se3::se3_exp_times;
-using wc::block_total;
-using wc::blocks_for;
-using wc::global_tid;
-using wc::HostRec;
-using wc::kCtlBytes;
+using namespace orbgpu::ba_phases;  // the kernels, their Args and Ctl, the field offsets
 
-constexpr int kThreads = 256;
 constexpr int kEdgeD = 67, kPointI = 2;  // doubles per edge, ints per point: ba_schur_device.h's fields alone
-
-// the optimisation's state on the device (wholechip::CtlBase's members and computeLambdaInit's maximum);
-// zeroed by the call, then written by one lane of one kernel at a time
-struct Ctl {
-    lm::Run run;
-    unsigned long long max_bits;  // computeLambdaInit's maximum, as bits
-    double first_chi;
-    int bad, fail, nf, n_active;
-};
-static_assert(sizeof(Ctl) <= kCtlBytes, "Ctl outgrew its slot");
 
 struct Layout {
     size_t P, M, E, n_max;                            // n_max = 6 P
@@ -125,386 +105,7 @@ inline Layout make_layout(int n_poses, int n_points, int n_edges) {
     return l;
 }
 
-// what every kernel gets
-struct Args {
-    int P, M, E, robust;
-    const float *Tcw, *cam, *Xw, *obs, *inv_sigma2;
-    const uint8_t* fixed;
-    const int *edge_pose, *edge_point;
-    float *Tcw_out, *Xw_out;
-    Ctl* ctl;
-    HostRec* rec;
-    double *wp, *wl, *we, *S, *x, *chi_part, *scale_part;
-    int *ip, *il, *ie;
-    int n_chi, n_scale;
-    double delta_mono, delta_stereo, dsqr_mono, dsqr_stereo;
-};
-
-#define PD(f, p) A.wp[(size_t)(f) * A.P + (p)]
-#define LD(f, m) A.wl[(size_t)(f) * A.M + (m)]
-#define ED(f, e) A.we[(size_t)(f) * A.E + (e)]
-#define PI(f, p) A.ip[(size_t)(f) * A.P + (p)]
-#define LI(f, m) A.il[(size_t)(f) * A.M + (m)]
-
-// ------------------------------------------------------------------ once per call: check and structure
-
-// an edge index out of range or edge_point decreasing: nothing else may index with these arrays
-__global__ __launch_bounds__(kThreads) void ba_check(Args A) {
-    const size_t i = global_tid();
-    if (i >= (size_t)A.E) return;
-    const int p = A.edge_pose[i], m = A.edge_point[i];
-    if (p < 0 || p >= A.P || m < 0 || m >= A.M || (i > 0 && A.edge_point[i - 1] > m)) A.ctl->bad = 1;
-}
-
-// Converter::toSE3Quat of every pose, every point widened; the counters cleared
-__global__ __launch_bounds__(kThreads) void ba_init(Args A) {
-    const size_t i = global_tid();
-    if (i < (size_t)A.P) {
-        const int p = (int)i;
-        double q[4], t[3];
-        orbgpu::se3::pose_from_T12(A.Tcw + 12 * i, q, t);
-        for (int k = 0; k < 4; ++k) PD(P_EST + k, p) = q[k];
-        for (int r = 0; r < 3; ++r) PD(P_EST + 4 + r, p) = t[r];
-        PI(IP_COUNT, p) = 0;
-    }
-    if (i < (size_t)A.M) {
-        const int m = (int)i;
-        for (int k = 0; k < 3; ++k) LD(L_EST + k, m) = (double)A.Xw[3 * i + k];
-        LI(IL_FIRST, m) = 0, LI(IL_END, m) = 0;
-    }
-}
-
-// a point's run of edges, the number of edges of every pose and of points with an edge (integer atomics)
-__global__ __launch_bounds__(kThreads) void ba_runs(Args A) {
-    if (A.ctl->bad) return;
-    const size_t gi = global_tid();
-    if (gi >= (size_t)A.E) return;
-    const int i = (int)gi, m = A.edge_point[i];
-    if (i == 0 || A.edge_point[i - 1] != m) LI(IL_FIRST, m) = i;
-    if (i == A.E - 1 || A.edge_point[i + 1] != m) {
-        LI(IL_END, m) = i + 1;
-        atomicAdd(&A.ctl->n_active, 1);
-    }
-    atomicAdd(&PI(IP_COUNT, A.edge_pose[i]), 1);
-}
-
-// where each pose's edge list starts, which poses are free, their order in the reduced system; one lane
-__global__ void ba_scan(Args A) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    HostRec* rec = A.rec;
-    rec->bad = A.ctl->bad;
-    if (A.ctl->bad) {
-        rec->nf = 0, rec->n_active = 0;
-        __threadfence_system();
-        return;
-    }
-    int s = 0, nf = 0;
-    for (int p = 0; p < A.P; ++p) {
-        const int count = PI(IP_COUNT, p);
-        PI(IP_START, p) = s;
-        s += count;
-        const int is_free = count > 0 && !A.fixed[p];
-        PI(IP_FREE, p) = is_free;
-        PI(IP_HIDX, p) = -1;
-        if (is_free) PI(IP_HIDX, p) = nf, PI(IP_HLIST, nf) = p, ++nf;
-    }
-    A.ctl->nf = nf;
-    rec->nf = nf, rec->n_active = A.ctl->n_active;
-    __threadfence_system();
-}
-
-// the pose-major edge list, ascending: one wave per pose scans the edges 64 at a time
-__global__ __launch_bounds__(kThreads) void ba_lists(Args A) {
-    if (A.ctl->bad) return;
-    const int lane = threadIdx.x & 63;
-    const int p = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-    if (p >= A.P) return;  // a whole wave
-    int before = PI(IP_START, p);
-    for (int i0 = 0; i0 < A.E; i0 += 64) {
-        const int i = i0 + lane;
-        const bool mine = i < A.E && A.edge_pose[i] == p;
-        const unsigned long long mask = __ballot(mine);
-        if (mine) A.ie[before + (int)__popcll(mask & ((1ull << lane) - 1))] = i;
-        before += (int)__popcll(mask);
-    }
-}
-
-// ------------------------------------------------------------------ per iteration and per trial: the edges
-
-// computeError of edge i at the estimates in field est_p / est_l: chi2, camera-frame point
-__device__ inline double edge_error(const Args& A, int i, int est_p, int est_l, double& x, double& y, double& z,
-                                    double (&e)[3], double (&q)[4], double& w, bool& stereo, const float*& cam) {
-    const int p = A.edge_pose[i], m = A.edge_point[i];
-    double t[3];
-    for (int k = 0; k < 4; ++k) q[k] = PD(est_p + k, p);
-    for (int k = 0; k < 3; ++k) t[k] = PD(est_p + 4 + k, p);
-    double r0, r1, r2;
-    lm::quat_rotate(q, LD(est_l, m), LD(est_l + 1, m), LD(est_l + 2, m), r0, r1, r2);
-    x = r0 + t[0], y = r1 + t[1], z = r2 + t[2];
-    cam = A.cam + 5 * (size_t)p;
-    const double fx = (double)cam[0], fy = (double)cam[1], cx = (double)cam[2], cy = (double)cam[3];
-    const float* ob = A.obs + 3 * (size_t)i;
-    w = (double)A.inv_sigma2[i];
-    stereo = ob[2] >= 0.0f;
-    if (stereo) {
-        const double bf = (double)cam[4];
-        const double invzf = (double)(float)(1.0 / z);  // const float invz = 1.0f / trans_xyz[2]
-        const double us = (x * invzf) * fx + cx;
-        const double vs = (y * invzf) * fy + cy;
-        const double rs = us - bf * invzf;
-        e[0] = (double)ob[0] - us;
-        e[1] = (double)ob[1] - vs;
-        e[2] = (double)ob[2] - rs;
-        return (e[0] * (w * e[0]) + e[1] * (w * e[1])) + e[2] * (w * e[2]);
-    }
-    e[0] = (double)ob[0] - ((x / z) * fx + cx);
-    e[1] = (double)ob[1] - ((y / z) * fy + cy);
-    e[2] = 0.0;
-    return e[0] * (w * e[0]) + e[1] * (w * e[1]);
-}
-
-// computeActiveErrors (+ linearizeOplus and the per-edge terms of buildSystem when kBuild) at the
-// estimates (kBuild) or the trial; the workgroup's robust chi2 goes to chi_part[blockIdx.x]
-template <bool kBuild>
-__global__ __launch_bounds__(kThreads) void ba_edges(Args A) {
-    __shared__ double s_val[kThreads];
-    __shared__ double s_row[16];
-    if (!kBuild && A.ctl->fail) return;
-    const size_t gi = global_tid();
-    double rho0 = 0.0;
-    if (gi < (size_t)A.E) {
-        const int i = (int)gi;
-        double x, y, z, e[3], q[4], w;
-        bool stereo;
-        const float* cam;
-        const double chi2 = edge_error(A, i, kBuild ? P_EST : P_TRIAL, kBuild ? L_EST : L_TRIAL, x, y, z, e, q, w, stereo,
-                                       cam);
-        double rho1 = 1.0;
-        rho0 = chi2;
-        if (A.robust)
-            lm::huber(chi2, stereo ? A.delta_stereo : A.delta_mono, stereo ? A.dsqr_stereo : A.dsqr_mono, rho0, rho1);
-        if (kBuild) {
-            const double fx = (double)cam[0], fy = (double)cam[1], bf = (double)cam[4];
-            double R[3][3], Jl[3][3], Jp[3][6];
-            quat_to_R(q, R);
-            const double z_2 = z * z;
-            if (stereo) {
-                for (int col = 0; col < 3; ++col) {
-                    Jl[0][col] = ((-fx) * R[0][col]) / z + ((fx * x) * R[2][col]) / z_2;
-                    Jl[1][col] = ((-fy) * R[1][col]) / z + ((fy * y) * R[2][col]) / z_2;
-                    Jl[2][col] = Jl[0][col] - (bf * R[2][col]) / z_2;
-                }
-            } else {  // -1./z * tmp * R
-                const double s = -1.0 / z;
-                const double t00 = s * fx, t01 = s * 0.0, t02 = s * (((-x) / z) * fx);
-                const double t10 = s * 0.0, t11 = s * fy, t12 = s * (((-y) / z) * fy);
-                for (int col = 0; col < 3; ++col) {
-                    Jl[0][col] = (t00 * R[0][col] + t01 * R[1][col]) + t02 * R[2][col];
-                    Jl[1][col] = (t10 * R[0][col] + t11 * R[1][col]) + t12 * R[2][col];
-                    Jl[2][col] = 0.0;
-                }
-            }
-            Jp[0][0] = ((x * y) / z_2) * fx;
-            Jp[0][1] = (-(1.0 + (x * x) / z_2)) * fx;
-            Jp[0][2] = (y / z) * fx;
-            Jp[0][3] = (-1.0 / z) * fx;
-            Jp[0][4] = 0.0;
-            Jp[0][5] = (x / z_2) * fx;
-            Jp[1][0] = (1.0 + (y * y) / z_2) * fy;
-            Jp[1][1] = (((-x) * y) / z_2) * fy;
-            Jp[1][2] = ((-x) / z) * fy;
-            Jp[1][3] = 0.0;
-            Jp[1][4] = (-1.0 / z) * fy;
-            Jp[1][5] = (y / z_2) * fy;
-            if (stereo) {
-                Jp[2][0] = Jp[0][0] - (bf * y) / z_2;
-                Jp[2][1] = Jp[0][1] + (bf * x) / z_2;
-                Jp[2][2] = Jp[0][2];
-                Jp[2][3] = Jp[0][3];
-                Jp[2][4] = 0.0;
-                Jp[2][5] = Jp[0][5] - bf / z_2;
-            } else {
-                for (int k = 0; k < 6; ++k) Jp[2][k] = 0.0;
-            }
-            const double Wt = rho1 * w;
-            ED(E_W, i) = Wt;
-            for (int r = 0; r < 3; ++r) {
-                ED(E_OMR + r, i) = rho1 * (-(w * e[r]));
-                for (int k = 0; k < 6; ++k) ED(E_JP + 6 * r + k, i) = Jp[r][k];
-                for (int k = 0; k < 3; ++k) ED(E_JL + 3 * r + k, i) = Jl[r][k];
-            }
-            for (int a = 0; a < 6; ++a)
-                for (int col = 0; col < 3; ++col)
-                    ED(E_B + 3 * a + col, i) = ((Wt * Jp[0][a]) * Jl[0][col] + (Wt * Jp[1][a]) * Jl[1][col]) +
-                                               (Wt * Jp[2][a]) * Jl[2][col];
-        }
-    }
-    const double total = block_total(rho0, s_val, s_row);
-    if (threadIdx.x == 0) A.chi_part[blockIdx.x] = total;
-}
-
-__device__ inline void note_diagonal(const Args& A, double h) {
-    atomicMax(&A.ctl->max_bits, (unsigned long long)__double_as_longlong(fabs(h)));
-}
-
-// the diagonal blocks and right-hand sides of buildSystem: one lane per entry, 27 per pose, then 9
-// per point; in the first iteration the diagonal entries enter computeLambdaInit's maximum
-__global__ __launch_bounds__(kThreads) void ba_vertex_sums(Args A, int first) {
-    const size_t gi = global_tid();
-    const size_t n_pose = (size_t)A.P * 27;
-    if (gi < n_pose) {
-        const int p = (int)(gi / 27), v = (int)(gi % 27);
-        if (!PI(IP_FREE, p)) return;
-        const int start = PI(IP_START, p), count = PI(IP_COUNT, p);
-        double acc = 0.0;
-        if (v < 21) {
-            int j, k;
-            upper_jk<6>(v, j, k);
-            for (int s = 0; s < count; ++s) {
-                const int e = A.ie[start + s];
-                const double Wt = ED(E_W, e);
-                acc += ((Wt * ED(E_JP + j, e)) * ED(E_JP + k, e) + (Wt * ED(E_JP + 6 + j, e)) * ED(E_JP + 6 + k, e)) +
-                       (Wt * ED(E_JP + 12 + j, e)) * ED(E_JP + 12 + k, e);
-            }
-            if (first && j == k) note_diagonal(A, acc);
-        } else {
-            const int j = v - 21;
-            for (int s = 0; s < count; ++s) {
-                const int e = A.ie[start + s];
-                acc += (ED(E_JP + j, e) * ED(E_OMR, e) + ED(E_JP + 6 + j, e) * ED(E_OMR + 1, e)) +
-                       ED(E_JP + 12 + j, e) * ED(E_OMR + 2, e);
-            }
-        }
-        PD(P_H + v, p) = acc;
-        return;
-    }
-    const size_t li = gi - n_pose;
-    if (li >= (size_t)A.M * 9) return;
-    const int m = (int)(li / 9), v = (int)(li % 9);
-    const int begin = LI(IL_FIRST, m), end = LI(IL_END, m);
-    if (end <= begin) return;
-    double acc = 0.0;
-    if (v < 6) {
-        int j, k;
-        upper_jk<3>(v, j, k);
-        for (int e = begin; e < end; ++e) {
-            const double Wt = ED(E_W, e);
-            acc += ((Wt * ED(E_JL + j, e)) * ED(E_JL + k, e) + (Wt * ED(E_JL + 3 + j, e)) * ED(E_JL + 3 + k, e)) +
-                   (Wt * ED(E_JL + 6 + j, e)) * ED(E_JL + 6 + k, e);
-        }
-        if (first && j == k) note_diagonal(A, acc);
-    } else {
-        const int j = v - 6;
-        for (int e = begin; e < end; ++e)
-            acc += (ED(E_JL + j, e) * ED(E_OMR, e) + ED(E_JL + 3 + j, e) * ED(E_OMR + 1, e)) +
-                   ED(E_JL + 6 + j, e) * ED(E_OMR + 2, e);
-    }
-    LD(L_H + v, m) = acc;
-}
-
-// the iteration begins: the robust chi2 at the kept estimates, computeLambdaInit in the first
-__global__ void ba_begin(Args A, int first) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    Ctl& c = *A.ctl;
-    wc::begin_iteration(c, A.chi_part, A.n_chi, first, [&c](lm::Run& run) {
-        lm::run_init_lambda(run, __longlong_as_double((long long)c.max_bits));
-    });
-}
-
-// Dinv = (Hll + lambda I)^-1 from cofactors and Dinv b_l, one lane per point
-__global__ __launch_bounds__(kThreads) void ba_point_inverse(Args A) {
-    const size_t gi = global_tid();
-    if (gi >= (size_t)A.M) return;
-    const int m = (int)gi;
-    if (LI(IL_END, m) <= LI(IL_FIRST, m)) return;
-    const double lambda = A.ctl->run.lambda;
-    const double a = LD(L_H, m) + lambda, b = LD(L_H + 1, m), cc = LD(L_H + 2, m);
-    const double d = LD(L_H + 3, m) + lambda, e = LD(L_H + 4, m), f = LD(L_H + 5, m) + lambda;
-    const double c00 = d * f - e * e, c01 = cc * e - b * f, c02 = b * e - cc * d;
-    const double c11 = a * f - cc * cc, c12 = b * cc - a * e, c22 = a * d - b * b;
-    const double inv = 1.0 / ((a * c00 + b * c01) + cc * c02);
-    const double D[3][3] = {{c00 * inv, c01 * inv, c02 * inv}, {c01 * inv, c11 * inv, c12 * inv}, {c02 * inv, c12 * inv, c22 * inv}};
-    LD(L_DINV, m) = D[0][0], LD(L_DINV + 1, m) = D[0][1], LD(L_DINV + 2, m) = D[0][2];
-    LD(L_DINV + 3, m) = D[1][1], LD(L_DINV + 4, m) = D[1][2], LD(L_DINV + 5, m) = D[2][2];
-    const double b0 = LD(L_H + 6, m), b1 = LD(L_H + 7, m), b2 = LD(L_H + 8, m);
-    for (int k = 0; k < 3; ++k) LD(L_V + k, m) = (D[k][0] * b0 + D[k][1] * b1) + D[k][2] * b2;
-}
-
-// Dinv (row-major, symmetric) of point m from its six stored entries
-__device__ inline void load_dinv(const Args& A, int m, double (&D)[3][3]) {
-    D[0][0] = LD(L_DINV, m), D[0][1] = LD(L_DINV + 1, m), D[0][2] = LD(L_DINV + 2, m);
-    D[1][1] = LD(L_DINV + 3, m), D[1][2] = LD(L_DINV + 4, m), D[2][2] = LD(L_DINV + 5, m);
-    D[1][0] = D[0][1], D[2][0] = D[0][2], D[2][1] = D[1][2];
-}
-
-// B Dinv of every edge that has a B (its pose is free), one lane per edge
-__global__ __launch_bounds__(kThreads) void ba_edge_bd(Args A) {
-    const size_t gi = global_tid();
-    if (gi >= (size_t)A.E) return;
-    const int i = (int)gi;
-    if (!PI(IP_FREE, A.edge_pose[i])) return;
-    double D[3][3];
-    load_dinv(A, A.edge_point[i], D);
-    for (int a = 0; a < 6; ++a) {
-        const double b0 = ED(E_B + 3 * a, i), b1 = ED(E_B + 3 * a + 1, i), b2 = ED(E_B + 3 * a + 2, i);
-        for (int k = 0; k < 3; ++k) ED(E_BD + 3 * a + k, i) = (b0 * D[0][k] + b1 * D[1][k]) + b2 * D[2][k];
-    }
-}
-
-// S = Hpp + lambda I - sum (B Dinv) B^T and b_schur = b_p - sum B (Dinv b_l).  The matrix is kept as
-// its lower triangle, rows of n = 6 nf doubles, b_schur being row n: entry (r, s) of block (a, b >= a)
-// lives at row 6 b + s, column 6 a + r.  36 lanes per block; then one lane per entry of b_schur.
-__global__ __launch_bounds__(kThreads) void ba_schur(Args A) {
-    const int nf = A.ctl->nf;
-    const size_t n = 6 * (size_t)nf;
-    const size_t gi = global_tid();
-    const size_t n_block_lanes = (size_t)nf * nf * 36;
-    const int* epoint = A.edge_point;
-    if (gi < n_block_lanes) {
-        const size_t blk = gi / 36;
-        const int l = (int)(gi % 36), r = l / 6, s = l % 6;
-        const int ia = (int)(blk / nf), ib = (int)(blk % nf);
-        if (ib < ia || (ib == ia && s < r)) return;
-        const int pa = PI(IP_HLIST, ia), pb = PI(IP_HLIST, ib);
-        double h = 0.0;
-        if (ib == ia) {
-            h = PD(P_H + lm::upper_index<6>(r, s), pa);
-            if (s == r) h = h + A.ctl->run.lambda;
-        }
-        const int sa = PI(IP_START, pa), ca = PI(IP_COUNT, pa), sb = PI(IP_START, pb), cb = PI(IP_COUNT, pb);
-        int jb = 0;
-        for (int ka = 0; ka < ca; ++ka) {  // the two lists ascend in the edge index, so in the point index
-            const int e = A.ie[sa + ka], m = epoint[e];
-            while (jb < cb && epoint[A.ie[sb + jb]] < m) ++jb;
-            if (jb >= cb) break;
-            if (epoint[A.ie[sb + jb]] != m) continue;
-            const double d0 = ED(E_BD + 3 * r, e), d1 = ED(E_BD + 3 * r + 1, e), d2 = ED(E_BD + 3 * r + 2, e);
-            for (int j2 = jb; j2 < cb; ++j2) {
-                const int e2 = A.ie[sb + j2];
-                if (epoint[e2] != m) break;
-                h -= (d0 * ED(E_B + 3 * s, e2) + d1 * ED(E_B + 3 * s + 1, e2)) + d2 * ED(E_B + 3 * s + 2, e2);
-            }
-        }
-        A.S[((size_t)6 * ib + s) * n + (size_t)6 * ia + r] = h;
-        return;
-    }
-    const size_t wi = gi - n_block_lanes;
-    if (wi >= n) return;
-    const int ia = (int)(wi / 6), j = (int)(wi % 6);
-    const int pa = PI(IP_HLIST, ia);
-    const int start = PI(IP_START, pa), count = PI(IP_COUNT, pa);
-    double coef = 0.0;
-    for (int k = 0; k < count; ++k) {
-        const int e = A.ie[start + k], m = epoint[e];
-        coef += (ED(E_B + 3 * j, e) * LD(L_V, m) + ED(E_B + 3 * j + 1, e) * LD(L_V + 1, m)) +
-                ED(E_B + 3 * j + 2, e) * LD(L_V + 2, m);
-    }
-    A.S[n * n + wi] = PD(P_H + 21 + j, pa) - coef;
-}
-
-// ------------------------------------------------------------------ the blocked Cholesky: chol_blocked.h
-
-// what its kernels read of the workspace
+// what chol_blocked.h's kernels read of the workspace
 struct SystemView {
     double *S, *x;
     int* fail;
@@ -512,103 +113,24 @@ struct SystemView {
     __device__ size_t n() const { return 6 * (size_t)*nf; }
 };
 
-// ------------------------------------------------------------------ the step, the trial, the judge
-
-// x_l = Dinv (b_l - B^T x_p), one lane per point; zero after a failed solve
-__global__ __launch_bounds__(kThreads) void ba_point_x(Args A) {
-    const size_t gi = global_tid();
-    if (gi >= (size_t)A.M) return;
-    const int m = (int)gi;
-    const int begin = LI(IL_FIRST, m), end = LI(IL_END, m);
-    if (end <= begin) return;
-    if (A.ctl->fail) {
-        for (int k = 0; k < 3; ++k) LD(L_X + k, m) = 0.0;
-        return;
-    }
-    double t[3] = {LD(L_H + 6, m), LD(L_H + 7, m), LD(L_H + 8, m)};
-    for (int e = begin; e < end; ++e) {
-        const int p = A.edge_pose[e];
-        if (!PI(IP_FREE, p)) continue;
-        const double* xp = A.x + 6 * (size_t)PI(IP_HIDX, p);
-        for (int k = 0; k < 3; ++k) {
-            double dot = ED(E_B + k, e) * xp[0];
-            for (int a = 1; a < 6; ++a) dot = dot + ED(E_B + 3 * a + k, e) * xp[a];
-            t[k] -= dot;
-        }
-    }
-    double D[3][3];
-    load_dinv(A, m, D);
-    for (int k = 0; k < 3; ++k) LD(L_X + k, m) = (D[k][0] * t[0] + D[k][1] * t[1]) + D[k][2] * t[2];
-}
-
-// trial = oplus(x) on the estimates, one lane per vertex (the poses, then the points), and the
-// vertex's terms of computeScale's sum; the workgroup's sum goes to scale_part[blockIdx.x]
-__global__ __launch_bounds__(kThreads) void ba_trial(Args A) {
-    __shared__ double s_val[kThreads];
-    __shared__ double s_row[16];
-    const size_t gi = global_tid();
-    const bool ok = !A.ctl->fail;
-    const double lambda = A.ctl->run.lambda;
-    double acc = 0.0;
-    if (gi < (size_t)A.P) {
-        const int p = (int)gi;
-        double q[4], t[3];
-        for (int k = 0; k < 4; ++k) q[k] = PD(P_EST + k, p);
-        for (int k = 0; k < 3; ++k) t[k] = PD(P_EST + 4 + k, p);
-        if (ok && PI(IP_FREE, p)) {
-            const double* xp = A.x + 6 * (size_t)PI(IP_HIDX, p);
-            const double x[6] = {xp[0], xp[1], xp[2], xp[3], xp[4], xp[5]};
-            double oq[4], ot[3];
-            se3_exp_times(q, t, x, oq, ot);
-            for (int k = 0; k < 4; ++k) q[k] = oq[k];
-            for (int k = 0; k < 3; ++k) t[k] = ot[k];
-            for (int k = 0; k < 6; ++k) acc += x[k] * (lambda * x[k] + PD(P_H + 21 + k, p));
-        }
-        for (int k = 0; k < 4; ++k) PD(P_TRIAL + k, p) = q[k];
-        for (int k = 0; k < 3; ++k) PD(P_TRIAL + 4 + k, p) = t[k];
-    } else if (gi < (size_t)A.P + A.M) {
-        const int m = (int)(gi - A.P);
-        const bool moved = ok && LI(IL_END, m) > LI(IL_FIRST, m);
-        for (int k = 0; k < 3; ++k) {
-            const double est = LD(L_EST + k, m);
-            if (moved) {
-                const double x = LD(L_X + k, m);
-                LD(L_TRIAL + k, m) = est + x;
-                acc += x * (lambda * x + LD(L_H + 6 + k, m));
-            } else {
-                LD(L_TRIAL + k, m) = est;
-            }
-        }
-    }
-    const double total = block_total(acc, s_val, s_row);
-    if (threadIdx.x == 0) A.scale_part[blockIdx.x] = total;
-}
-
-// OptimizationAlgorithmLevenberg::solve's decisions after a trial, by one lane; the host reads rec
-__global__ void ba_judge(Args A, int max_iter) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    wc::judge(*A.ctl, A.rec, A.chi_part, A.n_chi, A.scale_part, A.n_scale, max_iter);
-}
-
-// an accepted trial becomes the estimate
-__global__ __launch_bounds__(kThreads) void ba_accept(Args A) {
-    const size_t gi = global_tid();
-    if (gi < (size_t)A.P * 7) A.wp[(size_t)P_EST * A.P + gi] = A.wp[(size_t)P_TRIAL * A.P + gi];
-    if (gi < (size_t)A.M * 3) A.wl[(size_t)L_EST * A.M + gi] = A.wl[(size_t)L_TRIAL * A.M + gi];
-}
-
-// Converter::toCvMat(SE3Quat) of every pose, every point narrowed
-__global__ __launch_bounds__(kThreads) void ba_write(Args A) {
-    const size_t gi = global_tid();
-    if (gi < (size_t)A.P) {
-        const int p = (int)gi;
-        const double q[4] = {PD(P_EST, p), PD(P_EST + 1, p), PD(P_EST + 2, p), PD(P_EST + 3, p)};
-        const double t[3] = {PD(P_EST + 4, p), PD(P_EST + 5, p), PD(P_EST + 6, p)};
-        lm::write_T16(q, t, 1.0, A.Tcw_out + 16 * gi);
-    }
-    if (gi < (size_t)A.M)
-        for (int k = 0; k < 3; ++k) A.Xw_out[3 * gi + k] = (float)LD(L_EST + k, (int)gi);
-}
+// the kernels: ba_phases.h's, over Args (no levels)
+constexpr auto k_check = ba_check<Args>;
+constexpr auto k_init = ba_init<Args>;
+constexpr auto k_runs = ba_runs<Args>;
+constexpr auto k_scan = ba_scan<Args>;
+constexpr auto k_lists = ba_lists<Args>;
+constexpr auto k_edges_build = ba_edges<Args, true>;
+constexpr auto k_edges_trial = ba_edges<Args, false>;
+constexpr auto k_vertex_sums = ba_vertex_sums<Args>;
+constexpr auto k_begin = ba_begin<Args>;
+constexpr auto k_point_inverse = ba_point_inverse<Args>;
+constexpr auto k_edge_bd = ba_edge_bd<Args>;
+constexpr auto k_schur = ba_schur<Args>;
+constexpr auto k_point_x = ba_point_x<Args>;
+constexpr auto k_trial = ba_trial<Args>;
+constexpr auto k_judge = ba_judge<Args>;
+constexpr auto k_accept = ba_accept<Args>;
+constexpr auto k_write = ba_write<Args>;
 
 #undef PD
 #undef LD
@@ -684,11 +206,11 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
     const dim3 T(kThreads);
     // once per call: the check, the estimates and the structure; one synchronisation
     ORB_HIP(hipMemsetAsync(a.ctl, 0, kCtlBytes, st));
-    if (E) ORB_LAUNCH(st, ba_check, dim3(blocks_for(E)), T, a);
-    if (P + M) ORB_LAUNCH(st, ba_init, dim3(blocks_for(P > M ? P : M)), T, a);
-    if (E) ORB_LAUNCH(st, ba_runs, dim3(blocks_for(E)), T, a);
-    ORB_LAUNCH(st, ba_scan, dim3(1), dim3(64), a);
-    if (E && P) ORB_LAUNCH(st, ba_lists, dim3(blocks_for(P, kThreads / 64)), T, a);
+    if (E) ORB_LAUNCH(st, k_check, dim3(blocks_for(E)), T, a);
+    if (P + M) ORB_LAUNCH(st, k_init, dim3(blocks_for(P > M ? P : M)), T, a);
+    if (E) ORB_LAUNCH(st, k_runs, dim3(blocks_for(E)), T, a);
+    ORB_LAUNCH(st, k_scan, dim3(1), dim3(64), a);
+    if (E && P) ORB_LAUNCH(st, k_lists, dim3(blocks_for(P, kThreads / 64)), T, a);
     ORB_HIP(hipStreamSynchronize(st));
     if (rec->bad) {
         result->status = -1;
@@ -707,23 +229,23 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
                 break;
             }
             if (done) break;
-            ORB_LAUNCH(st, ba_edges<true>, dim3(blocks_for(E)), T, a);
-            ORB_LAUNCH(st, ba_vertex_sums, dim3(blocks_for(P * 27 + M * 9)), T, a, it == 0 ? 1 : 0);
-            ORB_LAUNCH(st, ba_begin, dim3(1), dim3(64), a, it == 0 ? 1 : 0);
+            ORB_LAUNCH(st, k_edges_build, dim3(blocks_for(E)), T, a);
+            ORB_LAUNCH(st, k_vertex_sums, dim3(blocks_for(P * 27 + M * 9)), T, a, it == 0 ? 1 : 0);
+            ORB_LAUNCH(st, k_begin, dim3(1), dim3(64), a, it == 0 ? 1 : 0);
             iterations = it + 1;
             for (int trial = 0; trial < lm::kMaxTrials; ++trial) {
-                ORB_LAUNCH(st, ba_point_inverse, dim3(blocks_for(M)), T, a);
-                ORB_LAUNCH(st, ba_edge_bd, dim3(blocks_for(E)), T, a);
+                ORB_LAUNCH(st, k_point_inverse, dim3(blocks_for(M)), T, a);
+                ORB_LAUNCH(st, k_edge_bd, dim3(blocks_for(E)), T, a);
                 if (nf) {
-                    ORB_LAUNCH(st, ba_schur, dim3(blocks_for((size_t)nf * nf * 36 + n)), T, a);
+                    ORB_LAUNCH(st, k_schur, dim3(blocks_for((size_t)nf * nf * 36 + n)), T, a);
                     ORB_HIP(orbgpu::chol::enqueue_solve(view, n, st));
                 }
-                ORB_LAUNCH(st, ba_point_x, dim3(blocks_for(M)), T, a);
-                ORB_LAUNCH(st, ba_trial, dim3(blocks_for(P + M)), T, a);
-                ORB_LAUNCH(st, ba_edges<false>, dim3(blocks_for(E)), T, a);
-                ORB_LAUNCH(st, ba_judge, dim3(1), dim3(64), a, n_iterations);
+                ORB_LAUNCH(st, k_point_x, dim3(blocks_for(M)), T, a);
+                ORB_LAUNCH(st, k_trial, dim3(blocks_for(P + M)), T, a);
+                ORB_LAUNCH(st, k_edges_trial, dim3(blocks_for(E)), T, a);
+                ORB_LAUNCH(st, k_judge, dim3(1), dim3(64), a, n_iterations);
                 ORB_HIP(hipStreamSynchronize(st));
-                if (rec->accepted) ORB_LAUNCH(st, ba_accept, dim3(blocks_for(P * 7 > M * 3 ? P * 7 : M * 3)), T, a);
+                if (rec->accepted) ORB_LAUNCH(st, k_accept, dim3(blocks_for(P * 7 > M * 3 ? P * 7 : M * 3)), T, a);
                 if (!rec->more) break;
                 if (flag_set(stop_flag)) {  // optimization_algorithm_levenberg.cpp:149
                     stopped = 2;
@@ -735,7 +257,7 @@ extern "C" int orbgpu_bundle_adjustment_device(int n_poses, int n_points, int n_
             done = rec->done != 0;
         }
     }
-    if (P + M) ORB_LAUNCH(st, ba_write, dim3(blocks_for(P > M ? P : M)), T, a);
+    if (P + M) ORB_LAUNCH(st, k_write, dim3(blocks_for(P > M ? P : M)), T, a);
     ORB_HIP(hipStreamSynchronize(st));
     result->iterations = iterations;
     result->rejected = rec->rejected;

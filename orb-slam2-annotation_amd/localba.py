@@ -8,6 +8,10 @@ include/orbgpu_localba.h (Optimizer::LocalBundleAdjustment, src/Optimizer.cpp:
   on a stream, with a caller-provided workspace.
 * ``local_bundle_adjustment`` -- one neighbourhood: (Tcw of the local poses,
   Xw, erase, result).
+* ``local_ba_chip`` / ``local_ba_chip_device`` / ``chip_workspace_bytes`` -- one
+  neighbourhood spread over the whole chip (include/orbgpu_localba_chip.h,
+  csrc/localba_chip.hip), synchronous, with the stop flag polled as g2o polls
+  it; ``MapLocalBA.solve(chip=True)`` is the same between gather and collect.
 * ``make_jobs`` / ``make_batch`` -- job records, and the concatenated arrays of
   a list of problems.
 * ``MapMirrorBA`` / ``MapLocalBA`` -- against a ``track.MapMirror``
@@ -166,6 +170,92 @@ def local_bundle_adjustment(Tcw, fixed, cam, Xw, pose_idx, point_idx, obs, inv_s
     return T.reshape(-1, 4, 4).copy(), X, er.astype(bool), res[0]
 
 
+# ---- one neighbourhood over the whole chip, with the stop flag (include/orbgpu_localba_chip.h) ----
+
+class LocalBAChipResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int), ("rounds", ctypes.c_int), ("n_bad_first", ctypes.c_int),
+                ("n_erase", ctypes.c_int), ("stop_poll", ctypes.c_int), ("polls", ctypes.c_int),
+                ("lm_iterations", ctypes.c_int * 2), ("lm_rejected", ctypes.c_int * 2), ("stopped", ctypes.c_int * 2),
+                ("iterations_applied", ctypes.c_int * 2), ("n_free", ctypes.c_int * 2),
+                ("n_active_points", ctypes.c_int * 2)]
+
+
+CHIP_RESULT_DTYPE = np.dtype([("status", "<i4"), ("rounds", "<i4"), ("n_bad_first", "<i4"), ("n_erase", "<i4"),
+                              ("stop_poll", "<i4"), ("polls", "<i4"), ("lm_iterations", "<i4", (2,)),
+                              ("lm_rejected", "<i4", (2,)), ("stopped", "<i4", (2,)),
+                              ("iterations_applied", "<i4", (2,)), ("n_free", "<i4", (2,)),
+                              ("n_active_points", "<i4", (2,))])
+assert CHIP_RESULT_DTYPE.itemsize == ctypes.sizeof(LocalBAChipResult) == 72
+CHIP_ITERATIONS = (5, 10)  # Optimizer.cpp:760, 813
+_CHIP_BOUND = False
+
+
+def _chip_lib():
+    global _CHIP_BOUND
+    L = orbgpu.lib()
+    if not _CHIP_BOUND:
+        i, sz, vp = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p
+        L.orbgpu_local_ba_chip_workspace_bytes.argtypes = [i, i, i, i]
+        L.orbgpu_local_ba_chip_workspace_bytes.restype = sz
+        L.orbgpu_local_ba_chip_device.argtypes = [i, i, i, i] + [vp] * 8 + [i, i, vp, i] + [vp] * 5 + [sz, vp]
+        L.orbgpu_local_ba_chip.argtypes = [i, i, i, i] + [vp] * 8 + [i, i, vp, i] + [vp] * 5 + [sz]
+        _CHIP_BOUND = True
+    return L
+
+
+def chip_workspace_bytes(n_poses: int, n_local: int, n_points: int, n_edges: int) -> int:
+    return int(_chip_lib().orbgpu_local_ba_chip_workspace_bytes(n_poses, n_local, n_points, n_edges))
+
+
+def local_ba_chip(Tcw, fixed, cam, Xw, pose_idx, point_idx, obs, inv_sigma2, n_local, iterations=CHIP_ITERATIONS,
+                  stop=None, stop_at_poll=-1):
+    """Host form of orbgpu_local_ba_chip: one neighbourhood over the whole chip.  Returns (Tcw (n_local, 4, 4)
+    float32, Xw (M, 3) float32, erase (E) uint8, the CHIP_RESULT_DTYPE record).  stop: a globalba.StopFlag,
+    or None; stop_at_poll: the replay of a recorded run's stop_poll."""
+    _, a = make_batch([dict(Tcw=Tcw, fixed=fixed, cam=cam, Xw=Xw, pose_idx=pose_idx, point_idx=point_idx, obs=obs,
+                            inv_sigma2=inv_sigma2, n_local=n_local)])
+    tp, tm, te, nl = len(a["Tcw"]), len(a["Xw"]), len(a["obs"]), int(n_local)
+    if not (len(a["fixed"]) == len(a["cam"]) == tp and len(a["edge_pose"]) == len(a["edge_point"]) == te
+            and len(a["inv_sigma2"]) == te):
+        raise ValueError("pose arrays need one row per pose, edge arrays one row per edge")
+    T, X, er = np.zeros((max(nl, 0), 16), np.float32), np.zeros((tm, 3), np.float32), np.zeros(te, np.uint8)
+    res = np.zeros(1, CHIP_RESULT_DTYPE)
+    orbgpu._check(_chip_lib().orbgpu_local_ba_chip(
+        tp, nl, tm, te, *(a[n].ctypes.data for n, *_ in INPUTS), int(iterations[0]), int(iterations[1]),
+        stop.ptr if stop is not None else None, int(stop_at_poll), T.ctypes.data, X.ctypes.data, er.ctypes.data,
+        res.ctypes.data, None, 0), "orbgpu_local_ba_chip")
+    return T.reshape(-1, 4, 4), X, er, res[0]
+
+
+def local_ba_chip_device(Tcw, fixed, cam, Xw, edge_pose, edge_point, obs, inv_sigma2, n_local, Tcw_out, Xw_out, erase,
+                         workspace, iterations=CHIP_ITERATIONS, stream=None, stop=None, stop_at_poll=-1,
+                         n_poses=None, n_points=None, n_edges=None):
+    """Device form on torch tensors of one GPU, in local_ba_batch_device's shapes for one job: Tcw_out float32
+    (>= n_local, 16), Xw_out float32 (M, 3), erase uint8 (E); workspace: a contiguous uint8 tensor of at least
+    chip_workspace_bytes(P, n_local, M, E) bytes.  n_poses / n_points / n_edges: the job's counts when the
+    tensors are larger than the job (their leading rows are the job's).  Synchronous; its launches go to
+    `stream`.  Returns the CHIP_RESULT_DTYPE record."""
+    tp = Tcw.shape[0] if n_poses is None else int(n_poses)
+    tm = Xw.shape[0] if n_points is None else int(n_points)
+    te = obs.shape[0] if n_edges is None else int(n_edges)
+    for t, rows, cols, name in ((Tcw, tp, 12, "Tcw"), (fixed, tp, 0, "fixed"), (cam, tp, 5, "cam"), (Xw, tm, 3, "Xw"),
+                                (edge_pose, te, 0, "edge_pose"), (edge_point, te, 0, "edge_point"), (obs, te, 3, "obs"),
+                                (inv_sigma2, te, 0, "inv_sigma2"), (Tcw_out, int(n_local), 16, "Tcw_out"),
+                                (Xw_out, tm, 3, "Xw_out"), (erase, te, 0, "erase")):
+        if t.shape[0] < rows or tuple(t.shape[1:]) != ((cols,) if cols else ()) or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous tensor of at least {rows} rows of {cols or 1}")
+    if workspace.dim() != 1 or not workspace.is_contiguous() or workspace.element_size() != 1:
+        raise ValueError("workspace: expected a contiguous one-dimensional uint8 tensor")
+    res = np.zeros(1, CHIP_RESULT_DTYPE)
+    p = orbgpu._ptr
+    orbgpu._check(_chip_lib().orbgpu_local_ba_chip_device(
+        tp, int(n_local), tm, te, p(Tcw), p(fixed), p(cam), p(Xw), p(edge_pose), p(edge_point), p(obs), p(inv_sigma2),
+        int(iterations[0]), int(iterations[1]), stop.ptr if stop is not None else None, int(stop_at_poll), p(Tcw_out),
+        p(Xw_out), p(erase), res.ctypes.data, p(workspace), workspace.numel(), orbgpu._stream_ptr(stream)),
+        "orbgpu_local_ba_chip_device")
+    return res[0]
+
+
 # ---- against the map mirror: gather, solve, collect on one stream (include/orbgpu_localba_map.h) ----
 
 MAP_OK, MAP_CAPACITY, MAP_BAD_JOB = 0, 2, 3  # ORBGPU_LOCALBA_MAP_*
@@ -283,8 +373,44 @@ class MapLocalBA:
             self.t["ws"] = self._zeros((max(size, 8),), torch.uint8)
         return self.t["ws"]
 
-    def solve(self, stream=None) -> None:
-        """call solve_workspace() first when `stream` is not the current one: the allocation is on the current"""
+    def chip_workspace(self):
+        """local_ba_chip_device's workspace for one job of the strides' size, allocated at its first use"""
+        import torch
+        if "chip_ws" not in self.t:
+            S = self.strides
+            size = chip_workspace_bytes(S["pose"], S["kf"], S["point"], S["edge"])
+            self.t["chip_ws"] = self._zeros((max(size, 8),), torch.uint8)
+        return self.t["chip_ws"]
+
+    def _solve_chip(self, stream, stop) -> None:
+        """the single job over the whole chip: the gathered job record is read back (one small copy), the
+        call runs on the gathered arrays in place and leaves its outputs where collect() reads them;
+        chip_result is its record, or None for a job the gather rejected (no call is made)"""
+        import contextlib
+        import torch
+        if self.n != 1:
+            raise ValueError("chip=True takes a single job")
+        t = self.t
+        ws = self.chip_workspace()
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            j = t["jobs"][:1].cpu().numpy().reshape(-1).view(JOB_DTYPE)[0]
+        self.chip_result = None
+        if min(int(j[k]) for k in ("n_poses", "n_local", "n_points", "n_edges")) < 0:
+            return
+        po, lo, eo, oo = (int(j[k]) for k in ("pose_offset", "point_offset", "edge_offset", "out_pose_offset"))
+        off = {"poses": po, "points": lo, "edges": eo, "local": oo}
+        ins = [t[name][off[total]:] for name, _, _, total in INPUTS]
+        outs = [t[name][off[total]:] for name, _, _, total in OUTPUTS]
+        self.chip_result = local_ba_chip_device(*ins, int(j["n_local"]), *outs, ws, stream=stream, stop=stop,
+                                                n_poses=int(j["n_poses"]), n_points=int(j["n_points"]),
+                                                n_edges=int(j["n_edges"]))
+
+    def solve(self, stream=None, chip=False, stop=None) -> None:
+        """call solve_workspace() first when `stream` is not the current one: the allocation is on the current.
+        chip=True (a single job): orbgpu_local_ba_chip_device in place of the batched launch, synchronous,
+        with `stop` (a globalba.StopFlag) polled as g2o polls it; call chip_workspace() first likewise"""
+        if chip:
+            return self._solve_chip(stream, stop)
         t = self.t
         self.solve_workspace()
         local_ba_batch_device(t["jobs"][:self.n], *(t[name] for name, *_ in INPUTS), *(t[name] for name, *_ in OUTPUTS),

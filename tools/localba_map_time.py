@@ -16,6 +16,12 @@ Per case, medians over --reps rounds after --warmup, ms:
 and the ratio ((a) + (c)) / (b).
 
     python tools/localba_map_time.py [--reps 7] [--warmup 2] [--out FILE]   # one JSON line
+    python tools/localba_map_time.py --chip [--out FILE]   # the one job only: MapLocalBA.solve(chip=True)
+                                     # (csrc/localba_chip.hip, the whole chip) and solve() (one workgroup) on
+                                     # the same gathered arrays in the same process, alternating, and
+                                     # globalba's optimize(10) on them as one problem: 3 warm-up rounds, 9
+                                     # timed, a host clock around each synchronous call; FILE gets the result
+                                     # under "map_time"
 """
 import argparse
 import json
@@ -31,11 +37,67 @@ for p in (ROOT / "orb-slam2-annotation_amd", ROOT / "oracle", ROOT / "tests"):
 NL, NF, M, SEE = 30, 20, 3000, 0.135
 
 
+def chip_case(torch, localba, B, r, out):
+    """--chip: the gathered job through the whole chip and through one workgroup, alternating, and
+    globalba's optimize(10) on the same arrays (every pose past n_local fixed) for its ms per LM iteration"""
+    import numpy as np
+
+    import globalba
+    B.chip_workspace()
+    erase = {}
+    t = {"chip": [], "one_workgroup": [], "globalba": []}
+    tp, tm, te, nl = r.n_local + r.n_fixed, r.n_points, r.n_edges, r.n_local
+    fixed = B.t["fixed"][:tp].clone()
+    fixed[nl:] = 1
+    g_T = torch.zeros((tp, 16), dtype=torch.float32, device=fixed.device)
+    g_X = torch.zeros((tm, 3), dtype=torch.float32, device=fixed.device)
+    g_ws = torch.empty(globalba.workspace_bytes(tp, tm, te), dtype=torch.uint8, device=fixed.device)
+    g_in = [B.t[n][:{"poses": tp, "points": tm, "edges": te}[tot]] for n, _, _, tot in localba.INPUTS]
+    g_in[1] = fixed
+
+    def glob():
+        return globalba.bundle_adjustment_device(*g_in, 10, 0, g_T, g_X, g_ws)
+
+    for i in range(3 + 9):
+        for name, fn in (("chip", lambda: B.solve(chip=True)), ("one_workgroup", B.solve), ("globalba", glob)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rg = fn()
+            torch.cuda.synchronize()
+            if i >= 3:
+                t[name].append((time.perf_counter() - t0) * 1e3)
+            if name != "globalba":
+                erase[name] = B.t["erase"][:te].clone()
+    rc = B.chip_result
+    rb = B.host("results")[0]
+    res = {}
+    for name, its, rej in (("chip", [int(v) for v in rc["lm_iterations"]], [int(v) for v in rc["lm_rejected"]]),
+                           ("one_workgroup", [int(v) for v in rb["lm_iterations"]], [int(v) for v in rb["lm_rejected"]]),
+                           ("globalba", [int(rg["iterations"])], [int(rg["rejected"])])):
+        ms = np.array(t[name])
+        n = max(sum(its), 1)
+        res[name] = {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max()),
+                     "lm_iterations": its, "lm_rejected": rej, "ms_per_lm_iteration": float(np.median(ms)) / n,
+                     "spread_ms_per_lm_iteration": float(ms.max() - ms.min()) / n}
+    c, b, g = res["chip"], res["one_workgroup"], res["globalba"]
+    res["chip"].update(polls=int(rc["polls"]), rounds=int(rc["rounds"]), n_erase=int(rc["n_erase"]),
+                       n_free=[int(v) for v in rc["n_free"]])
+    res["per_iteration_ratio"] = b["ms_per_lm_iteration"] / c["ms_per_lm_iteration"]
+    res["whole_call_ratio"] = b["median_ms"] / c["median_ms"]
+    res["faster_by_more_than_both_spreads"] = bool(
+        b["ms_per_lm_iteration"] - c["ms_per_lm_iteration"] > c["spread_ms_per_lm_iteration"] + b["spread_ms_per_lm_iteration"])
+    res["chip_over_globalba_per_iteration"] = c["ms_per_lm_iteration"] / g["ms_per_lm_iteration"]
+    res["erase_equal"] = bool(torch.equal(erase["chip"], erase["one_workgroup"]))
+    out.update(shape="tools/localba_map_time.py one job", n_local=nl, n_fixed=r.n_fixed, n_points=tm, n_edges=te, **res)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--chip", action="store_true")
     a = ap.parse_args()
     import torch
 
@@ -93,6 +155,9 @@ def main():
         torch.cuda.synchronize()
         G = B.host("gather_results")
         assert (G["status"] == lr.OK).all() and [int(v) for v in G["n_edges"]] == [r.n_edges for r in refs]
+        if a.chip:
+            out = chip_case(torch, localba, B, refs[0], out)
+            break
         t_gather = events(B.gather)
         t_solve = events(B.solve)
         t_collect = events(lambda: B.collect(write_mirror=True))
@@ -109,7 +174,12 @@ def main():
                      "gather_plus_collect_over_solve": round((g + c) / s, 5)}
     line = json.dumps(out)
     print(line)
-    if a.out:
+    if a.out and a.chip:
+        path = Path(a.out)
+        doc = json.loads(path.read_text()) if path.exists() else {}
+        doc["map_time"] = out
+        path.write_text(json.dumps(doc, indent=1) + "\n")
+    elif a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(line + "\n")
 
