@@ -27,6 +27,7 @@
 //                          monocular pairs, CheckDistEpipolarLine :166-190).
 #include "../../include/orbgpu_bow.h"
 #include "bow_kernels.h"
+#include "bow_score.h"
 #include "device_state.h"
 
 namespace orbgpu {
@@ -775,7 +776,7 @@ __global__ __launch_bounds__(256) void bow_db_score_kernel(int scoring, const in
                                                            double* __restrict__ score) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= nkf) return;
-    const double LOG_EPS = log(2.220446049250313080847e-16);  // log(DBL_EPSILON)
+    const double LOG_EPS = bowscore::kl_log_eps();
     int i = 0, j = off[k];
     const int je = off[k + 1];
     double s = 0.0;
@@ -785,17 +786,13 @@ __global__ __launch_bounds__(256) void bow_db_score_kernel(int scoring, const in
         const double vi = qv[i], wi = dv[j];
         if (a == b) {
             ++nc;
-            switch (scoring) {
-                case 0: s += fabs(vi - wi) - fabs(vi) - fabs(wi); break;     // L1
-                case 1: case 5: s += vi * wi; break;                         // L2, dot product
-                case 2: if (vi + wi != 0.0) s += vi * wi / (vi + wi); break; // chi-square
-                case 3: if (vi != 0 && wi != 0) s += vi * log(vi / wi); break;  // KL
-                default: s += sqrt(vi * wi); break;                          // Bhattacharyya
-            }
+            bool add;
+            const double t = bowscore::common_term(scoring, vi, wi, &add);
+            if (add) s += t;
             ++i;
             ++j;
         } else if (a < b) {
-            if (scoring == 3) s += vi * (log(vi) - LOG_EPS);  // KL walks every query word
+            if (scoring == 3) s += bowscore::kl_query_only_term(vi, LOG_EPS);  // KL walks every query word
             ++i;
         } else {
             ++j;
@@ -803,10 +800,8 @@ __global__ __launch_bounds__(256) void bow_db_score_kernel(int scoring, const in
     }
     if (scoring == 3)
         for (; i < nq; ++i)
-            if (qv[i] != 0) s += qv[i] * (log(qv[i]) - LOG_EPS);
-    if (scoring == 0) s = -s / 2.0;
-    else if (scoring == 1) s = s >= 1 ? 1.0 : 1.0 - sqrt(1.0 - s);
-    else if (scoring == 2) s = 2. * s;
+            if (qv[i] != 0) s += bowscore::kl_query_only_term(qv[i], LOG_EPS);
+    s = bowscore::finish(scoring, s);
     // common words count every query word once (the inverted-file loop visits each
     // (word, keyframe) entry once)
     if (scoring == 3) {  // the KL walk advanced i past non-common words too: count separately

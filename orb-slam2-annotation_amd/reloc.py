@@ -181,6 +181,38 @@ class RelocBurst:
         self.rows = torch.zeros((Q, ROWS, S), dtype=torch.int32, device=dev)
         self.started = False
 
+    @classmethod
+    def from_tables(cls, frames: Frames, kfs: loop.Keyframes, search: loop.KeyframeSearch, tables, nnratio=0.75,
+                    check_ori=True):
+        """A burst over prepared device tables (kfdb.RelocTables, filled on the
+        device by kfdb.KeyFrameDatabase.emit_reloc): query q owns entries
+        [q * cand_stride, (q + 1) * cand_stride) and its candidates are known
+        on the device only, so ``pairs`` is not available.  Nothing is read
+        back or uploaded here."""
+        import torch
+        if frames.stride != kfs.stride:
+            raise ValueError("frames and keyframes must share the stride")
+        self = cls.__new__(cls)
+        self.frames, self.kfs, self.search = frames, kfs, search
+        self.nnratio, self.check_ori = nnratio, check_ori
+        dev, S = kfs.device, kfs.stride
+        self.n_queries, self.n_pairs = tables.n_queries, tables.n_queries * tables.cand_stride
+        self.pairs, self.tables = None, tables
+        P, Q = max(self.n_pairs, 1), max(self.n_queries, 1)
+        self.d_fa, self.d_fb, self.d_cands, self.d_queries = tables.d_fa, tables.d_fb, tables.d_cands, tables.d_queries
+        self.uploaded = False
+        self.match = torch.zeros((P, S), dtype=torch.int32, device=dev)
+        self.nmatches = torch.zeros(P, dtype=torch.int32, device=dev)
+        L = _lib()
+        self.n_corr = torch.zeros(P, dtype=torch.int32, device=dev)
+        self.workspace = torch.zeros(L.orbgpu_reloc_setup_workspace_bytes(P, S), dtype=torch.uint8, device=dev)
+        self.state = torch.zeros(L.orbgpu_relocalize_workspace_bytes(Q, P, S), dtype=torch.uint8, device=dev)
+        self.results = torch.zeros(Q * ctypes.sizeof(RelocResult), dtype=torch.uint8, device=dev)
+        self.cand_states = torch.zeros(P * ctypes.sizeof(RelocCandidateState), dtype=torch.uint8, device=dev)
+        self.rows = torch.zeros((Q, ROWS, S), dtype=torch.int32, device=dev)
+        self.started = False
+        return self
+
     def search_by_bow(self, stream=None):
         """SearchByBoW(pKF, mCurrentFrame, vvpMapPointMatches[i]) for every pair."""
         if self.uploaded:
