@@ -8,6 +8,11 @@ csrc/covis.hip), beside a ``track.MapMirror`` and a ``localba.MapMirrorBA``.
   are kept.
 * ``erase_keyframes`` -- the covisibility part of KeyFrame::SetBadFlag for a
   list of keyframes, asynchronous on the given stream.
+* ``update_connections`` -- KeyFrame::UpdateConnections for a list of keyframes
+  against a ``track.MapMirror``.
+* ``keyframe_culling`` -- the judging loop of LocalMapping::KeyFrameCulling
+  against the two mirrors and a ``MapMirrorCull``; ``Culling.erase`` hands its
+  culled rows to the erasure on the same stream.
 """
 from __future__ import annotations
 
@@ -17,8 +22,9 @@ import numpy as np
 
 import orbgpu
 
-OK, BAD_JOB = 0, 3                                     # ORBGPU_COVIS_*
-BEST, MAX_STRIDE = 10, 1024                            # ORBGPU_COVIS_BEST, _MAX_STRIDE
+OK, EMPTY, CAPACITY, BAD_JOB = 0, 1, 2, 3              # ORBGPU_COVIS_*
+KEPT, CULLED, TO_BE_ERASED, SKIPPED_FIRST = 0, 1, 2, 3 # ORBGPU_COVIS_CULL_*
+BEST, MAX_STRIDE, TH = 10, 1024, 15                    # ORBGPU_COVIS_BEST, _MAX_STRIDE, _TH
 _vp, _i = ctypes.c_void_p, ctypes.c_int
 _BOUND = False
 
@@ -28,11 +34,48 @@ class CovisGraphStruct(ctypes.Structure):
                 ("ord_kf", _vp), ("ord_w", _vp), ("covis10", _vp)]
 
 
+class UpdateResult(ctypes.Structure):
+    _fields_ = [("status", _i), ("n_counted", _i), ("n_ordered", _i), ("kf_max", _i), ("w_max", _i), ("front", _i),
+                ("pad", _i * 2)]
+
+
+class MapMirrorCullStruct(ctypes.Structure):
+    _fields_ = [("kp_octave", _vp), ("kp_depth", _vp), ("kf_th_depth", _vp), ("kf_not_erase", _vp)]
+
+
+class CullJob(ctypes.Structure):
+    _fields_ = [("kf", _i), ("mono", _i)]
+
+
+class CullVerdict(ctypes.Structure):
+    _fields_ = [("kf", _i), ("n_mps", _i), ("n_redundant", _i), ("verdict", _i)]
+
+
+class CullResult(ctypes.Structure):
+    _fields_ = [("status", _i), ("n_list", _i), ("n_culled", _i), ("n_to_be_erased", _i), ("pad", _i * 4)]
+
+
+UPDATE_RESULT_DTYPE = np.dtype([(name, "<i4") for name, _ in UpdateResult._fields_[:-1]] + [("pad", "<i4", (2,))])
+CULL_VERDICT_DTYPE = np.dtype([(name, "<i4") for name, _ in CullVerdict._fields_])
+CULL_RESULT_DTYPE = np.dtype([(name, "<i4") for name, _ in CullResult._fields_[:-1]] + [("pad", "<i4", (4,))])
+assert UPDATE_RESULT_DTYPE.itemsize == ctypes.sizeof(UpdateResult) == 32 and ctypes.sizeof(CullJob) == 8
+assert CULL_VERDICT_DTYPE.itemsize == ctypes.sizeof(CullVerdict) == 16
+assert CULL_RESULT_DTYPE.itemsize == ctypes.sizeof(CullResult) == 32
+
+
 def _lib():
     global _BOUND
     L = orbgpu.lib()
     if not _BOUND:
-        L.orbgpu_covis_erase_keyframes_batch_device.argtypes = [_i, _vp, ctypes.POINTER(CovisGraphStruct), _vp, _vp]
+        import localba
+        import track
+        G, M = ctypes.POINTER(CovisGraphStruct), ctypes.POINTER(track.MapMirrorStruct)
+        L.orbgpu_covis_erase_keyframes_batch_device.argtypes = [_i, _vp, G, _vp, _vp]
+        L.orbgpu_covis_update_workspace_bytes.argtypes = [_i, _i]
+        L.orbgpu_covis_update_workspace_bytes.restype = ctypes.c_size_t
+        L.orbgpu_covis_update_connections_batch_device.argtypes = [_i, _vp, M, G, _vp, ctypes.c_size_t, _vp, _vp]
+        L.orbgpu_covis_keyframe_culling_batch_device.argtypes = [
+            _i, _vp, M, ctypes.POINTER(localba.MapMirrorBAStruct), ctypes.POINTER(MapMirrorCullStruct), G, _i, _vp, _vp, _vp, _vp]
         _BOUND = True
     return L
 
@@ -122,3 +165,102 @@ def erase_keyframes(graph, kfs, stream=None, device="cuda"):
         "orbgpu_covis_erase_keyframes_batch_device")
     graph._erased = d_kfs  # the list stays allocated while the launch is in flight on another stream
     return status[:n]
+
+
+class MapMirrorCull:
+    """What KeyFrameCulling's judge reads beside a track.MapMirror and a localba.MapMirrorBA, uploaded from numpy:
+    kp_octave / kp_depth (per keyframe an (n_slots,) array, parallel to the mirror's slots), kf_th_depth and
+    kf_not_erase (n_kf,).  The caller keeps it current."""
+
+    def __init__(self, kp_octave, kp_depth, kf_th_depth, kf_not_erase, device="cuda"):
+        import track
+        flat = lambda rows, dt: np.concatenate([np.asarray(r, dt).reshape(-1) for r in rows] + [np.zeros(0, dt)])
+        host = {"kp_octave": (flat(kp_octave, np.uint8), np.uint8), "kp_depth": (flat(kp_depth, np.float32), np.float32),
+                "kf_th_depth": (kf_th_depth, np.float32), "kf_not_erase": (kf_not_erase, np.uint8)}
+        self.t = {name: track._up(a, dt, device) for name, (a, dt) in host.items()}
+        c = self.c = MapMirrorCullStruct()
+        for name, t in self.t.items():
+            setattr(c, name, track._ptr(t))
+
+
+def update_workspace_bytes(n: int, n_kf: int) -> int:
+    return int(_lib().orbgpu_covis_update_workspace_bytes(n, n_kf))
+
+
+def _on(stream):
+    import contextlib
+    import torch
+    return torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else contextlib.nullcontext()
+
+
+def update_connections(graph, mirror, kfs, stream=None, device="cuda"):
+    """orbgpu_covis_update_connections_batch_device for `kfs` in order on `graph` against the track.MapMirror
+    `mirror`; returns the results, a (n, 32) uint8 tensor to view as UPDATE_RESULT_DTYPE once downloaded"""
+    import torch
+    n = len(kfs)
+    need = update_workspace_bytes(n, graph.n_kf)
+    if n > 0 and need == 0:
+        raise ValueError("n * n_kf does not fit an int")
+    with _on(stream):  # the list is copied and the buffers allocated on the stream the launches run on
+        d_kfs = torch.from_numpy(np.asarray(list(kfs) + [0] * (n == 0), np.int32)).to(device)
+        results = torch.empty((max(n, 1), ctypes.sizeof(UpdateResult)), dtype=torch.uint8, device=device)  # every one is written
+        ws = torch.empty((max(need, 4),), dtype=torch.uint8, device=device)
+    orbgpu._check(_lib().orbgpu_covis_update_connections_batch_device(
+        n, orbgpu._ptr(d_kfs), ctypes.byref(mirror.c), ctypes.byref(graph.c), orbgpu._ptr(ws), ws.numel(), orbgpu._ptr(results),
+        orbgpu._stream_ptr(stream)), "orbgpu_covis_update_connections_batch_device")
+    graph._update = (d_kfs, ws, mirror)  # stay allocated while the launches are in flight on another stream
+    return results[:n]
+
+
+def update_results(results) -> np.ndarray:
+    """the downloaded results of update_connections as a record array"""
+    return results.cpu().numpy().reshape(-1).view(UPDATE_RESULT_DTYPE)
+
+
+class Culling:
+    """The buffers of one orbgpu_covis_keyframe_culling_batch_device call: results (n, 32) uint8, verdicts
+    (n, list_stride, 4) int32 and culled (n, list_stride) int32, which erase() hands unchanged to
+    orbgpu_covis_erase_keyframes_batch_device on the same stream."""
+
+    def __init__(self, graph, jobs, list_stride, stream, device, guard=None):
+        """guard: a byte to fill verdicts with before the launch, for a test of what the launch leaves alone"""
+        import torch
+        self.graph, self.n, self.list_stride, self.stream = graph, len(jobs), int(list_stride), stream
+        n = max(self.n, 1)
+        tab = np.zeros((n, 2), np.int32)
+        tab[:self.n] = np.asarray([(int(kf), int(bool(mono))) for kf, mono in jobs], np.int32).reshape(-1, 2)
+        with _on(stream):
+            self.jobs = torch.from_numpy(tab).to(device)
+            self.results = torch.empty((n, ctypes.sizeof(CullResult)), dtype=torch.uint8, device=device)
+            self.verdicts = torch.empty((n, self.list_stride, 4), dtype=torch.int32, device=device)
+            self.culled = torch.empty((n, self.list_stride), dtype=torch.int32, device=device)
+            self.status = torch.empty((n * self.list_stride,), dtype=torch.int32, device=device)
+            if guard is not None:
+                self.verdicts.view(torch.uint8).fill_(guard)
+
+    def erase(self):
+        """the graph side of the culled keyframes' SetBadFlag, with no download between the two calls; returns the
+        erasure's status per entry of `culled` (BAD_JOB where it holds -1)"""
+        m = self.n * self.list_stride
+        orbgpu._check(_lib().orbgpu_covis_erase_keyframes_batch_device(
+            m, orbgpu._ptr(self.culled), ctypes.byref(self.graph.c), orbgpu._ptr(self.status), orbgpu._stream_ptr(self.stream)),
+            "orbgpu_covis_erase_keyframes_batch_device")
+        return self.status[:m]
+
+    def host(self):
+        """(results as a record array, verdicts as a (n, list_stride) record array, culled) downloaded"""
+        r = self.results.cpu().numpy().reshape(-1).view(CULL_RESULT_DTYPE)[:self.n]
+        v = self.verdicts.cpu().numpy().reshape(-1).view(CULL_VERDICT_DTYPE).reshape(-1, self.list_stride)[:self.n]
+        return r, v, self.culled.cpu().numpy()[:self.n]
+
+
+def keyframe_culling(graph, mirror, mirror_ba, cull_mirror, jobs, stream=None, list_stride=None, device="cuda", guard=None):
+    """orbgpu_covis_keyframe_culling_batch_device for `jobs`, (kf, mono) pairs, each judged on its own; returns a
+    Culling.  list_stride: the graph's conn_stride when None."""
+    c = Culling(graph, jobs, graph.conn_stride if list_stride is None else list_stride, stream, device, guard)
+    orbgpu._check(_lib().orbgpu_covis_keyframe_culling_batch_device(
+        c.n, orbgpu._ptr(c.jobs), ctypes.byref(mirror.c), ctypes.byref(mirror_ba.c), ctypes.byref(cull_mirror.c),
+        ctypes.byref(graph.c), c.list_stride, orbgpu._ptr(c.results), orbgpu._ptr(c.verdicts), orbgpu._ptr(c.culled),
+        orbgpu._stream_ptr(stream)), "orbgpu_covis_keyframe_culling_batch_device")
+    c.mirrors = (mirror, mirror_ba, cull_mirror)  # stay allocated while the launch is in flight
+    return c
